@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — frames/sec of the MI355X 3DGS rasterizer (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|1]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|1] [--full] [--dump-outputs DIR]
 
 One step = one full frame through the native pipeline (preprocess -> depth
 sort -> tile binning: row pass + column pass -> blend) on the synthetic scene
@@ -17,9 +17,17 @@ nccl), issued asynchronously and overlapped with the next frame's render
 (double-buffered); --gather end hands over only the last frame, after the
 timed region.  gaussianrenderer_amd/multi.py holds the per-rank logic.
 
-Rank 0 prints ONE JSON line (contract in the task statement), including the
-blend kernel's roofline (HIP events around every blend launch inside the timed
-region) and the CPU-oracle baseline (rank 0, N = 1 only, bounded sample).
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run does only
+what the headline needs: scene, warmup, the K timed frames, the line.  --full adds
+every other measurement, in runs of their own around the timed region: the per-stage
+breakdown and blend counters, the one-at-a-time segment with the blend kernel's
+roofline (HIP events around its launches), the SH-3 and moving-camera
+sub-measurements, the drop-in call's rate, the N > 1 'scale' object and the
+CPU-oracle baseline (rank 0, N = 1 only, bounded sample).
+
+--dump-outputs DIR: rank 0 writes the last frame of the timed region (what a caller
+of the timed path receives: the planar fp32 image) as DIR/image.npy.  The scene is
+seeded, so two builds run with the same arguments can be compared pixel for pixel.
 """
 from __future__ import annotations
 
@@ -66,6 +74,12 @@ def parse():
     ap.add_argument("--k", type=float, default=3.0)
     ap.add_argument("--warm-ms", type=float, default=1000.0,
                     help="untimed frames in flight for at least this long right before the timed regions")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: stage times, blend counters and "
+                         "roofline, the one-at-a-time segment, the sh3 / orbit objects, the drop-in rate, "
+                         "the N>1 scale object, the CPU baseline (the --no-* options trim this set)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed frame (planar fp32 [3, H, W]) as DIR/image.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU-oracle sample length")
     ap.add_argument("--scene-dir", default=None)
@@ -613,40 +627,42 @@ def main():
         r.sync()
         return frames
 
-    warm(min(300.0, args.warm_ms))   # stage times below are taken on a warm card too
-
-    # untimed frames: the per-stage breakdown averaged over STAGE_FRAMES plain
-    # frames (events between stages), then P, Pc and the blend counters from the
-    # instrumented blend kernel
-    t_mid = frame_time(TIMESTEPS_4D // 2) if four_d else None
-    r.set_timing(2)
-    for i in range(STAGE_FRAMES):
-        r.render(scene, frame_cam(i) if frame_cam else cam, W, H, outs[0].data_ptr(), k=args.k, stream=stream,
-                 time=t_mid)
-    advance(STAGE_FRAMES)
-    r.sync()
-    stage_sums, stage_frames = r.stage_times()
-    stages = {k: v / max(1, stage_frames) for k, v in stage_sums.items()}
-    r.set_timing(0)
-    r.set_diagnostics(True)
-    r.render(scene, frame_cam(0) if frame_cam else cam, W, H, outs[0].data_ptr(), k=args.k, stream=stream,
-             time=t_mid)
-    advance(1)
-    r.sync()
-    pairs = r.pair_count()
-    row_items = r.row_item_count()
-    depth_passes = r.depth_passes()
-    counters = r.blend_counters_ex()
-    consumed = counters["records_loaded"]
+    full = args.full
     global BLEND_KERNEL
-    blend_exp = r.get_tuning(22)
-    split_state = r.get_tuning(26)                    # GSR_TUNE_DEPTH_SPLIT_STATE of the last frame
-    split = split_state != 0
-    BLEND_KERNEL = BLEND_KERNELS["split" if split else min(blend_exp, 1)]
-    r.set_diagnostics(False)
-    tiles_x, tiles_y = r.tile_grid()
-    # visible Gaussians M (depth key != 0xFFFFFFFF), untimed
-    visible = int((r.read_splats(n)["depth_key"] != 0xFFFFFFFF).sum())
+    if full:
+        warm(min(300.0, args.warm_ms))   # stage times below are taken on a warm card too
+
+        # untimed frames: the per-stage breakdown averaged over STAGE_FRAMES plain
+        # frames (events between stages), then P, Pc and the blend counters from the
+        # instrumented blend kernel
+        t_mid = frame_time(TIMESTEPS_4D // 2) if four_d else None
+        r.set_timing(2)
+        for i in range(STAGE_FRAMES):
+            r.render(scene, frame_cam(i) if frame_cam else cam, W, H, outs[0].data_ptr(), k=args.k, stream=stream,
+                     time=t_mid)
+        advance(STAGE_FRAMES)
+        r.sync()
+        stage_sums, stage_frames = r.stage_times()
+        stages = {k: v / max(1, stage_frames) for k, v in stage_sums.items()}
+        r.set_timing(0)
+        r.set_diagnostics(True)
+        r.render(scene, frame_cam(0) if frame_cam else cam, W, H, outs[0].data_ptr(), k=args.k, stream=stream,
+                 time=t_mid)
+        advance(1)
+        r.sync()
+        pairs = r.pair_count()
+        row_items = r.row_item_count()
+        depth_passes = r.depth_passes()
+        counters = r.blend_counters_ex()
+        consumed = counters["records_loaded"]
+        blend_exp = r.get_tuning(22)
+        split_state = r.get_tuning(26)                    # GSR_TUNE_DEPTH_SPLIT_STATE of the last frame
+        split = split_state != 0
+        BLEND_KERNEL = BLEND_KERNELS["split" if split else min(blend_exp, 1)]
+        r.set_diagnostics(False)
+        tiles_x, tiles_y = r.tile_grid()
+        # visible Gaussians M (depth key != 0xFFFFFFFF), untimed
+        visible = int((r.read_splats(n)["depth_key"] != 0xFFFFFFFF).sum())
 
     def timed(fn):
         if dist:
@@ -662,10 +678,12 @@ def main():
 
     # clocks and power before the timed regions (a ~1 s host-side child process, so it
     # runs before the sustained warmup, never between warmup and timing)
-    props = torch.cuda.get_device_properties(device)
-    pci = (f"{props.pci_domain_id:04x}:{props.pci_bus_id:02x}:{props.pci_device_id:02x}.0"
-           if hasattr(props, "pci_bus_id") else None)
-    telemetry_before = gpu_telemetry(pci) if rank == 0 else None
+    pci = None
+    if full:
+        props = torch.cuda.get_device_properties(device)
+        pci = (f"{props.pci_domain_id:04x}:{props.pci_bus_id:02x}:{props.pci_device_id:02x}.0"
+               if hasattr(props, "pci_bus_id") else None)
+    telemetry_before = gpu_telemetry(pci) if full and rank == 0 else None
     # sustained warmup: the card leaves its idle power state over tens of ms, so a
     # short K (the driver's --steps 20 is ~10 ms of frames) would otherwise be timed on
     # the ramp.  Frames in flight for at least --warm-ms of wall time, untimed.
@@ -676,18 +694,23 @@ def main():
     # sequential segment: K frames one at a time on one stream (the viewer's use and the
     # frame latency), HIP events around the blend launch of every TIMING_STRIDE-th frame
     # (an event pair per frame costs ~7 us; every frame is the same workload, so the
-    # sampled mean is the launch mean) -> roofline of the blend kernel running alone
-    r.set_timing(1, TIMING_STRIDE)
-
+    # sampled mean is the launch mean) -> roofline of the blend kernel running alone.
+    # A plain run skips it, unless it is the headline itself (one frame in flight), and
+    # then takes it without the events.
     def run_sequential():
         for i in range(args.steps):
             frame(i)
-    lead_in(True)
-    seq_elapsed = timed(run_sequential)
-    advance(args.steps)
-    blend_times, timed_frames = r.stage_times()
-    r.set_timing(0)
-    seq_overflow = r.sync()
+    seq_elapsed, seq_overflow = None, 0
+    if full or (F == 1 and not shard.validity):
+        if full:
+            r.set_timing(1, TIMING_STRIDE)
+        lead_in(True)
+        seq_elapsed = timed(run_sequential)
+        advance(args.steps)
+        if full:
+            blend_times, timed_frames = r.stage_times()
+            r.set_timing(0)
+        seq_overflow = r.sync()
 
     # pipelined timed region (the reported value): the same K frames through
     # gsr_render_path with F frames in flight (no timing events in it: lane 0's blend
@@ -723,8 +746,16 @@ def main():
     overflow = r.sync() or seq_overflow
     split_after = (r.get_tuning(26), r.get_tuning(24))   # depth split state and point after the timed frames
     bucket_over = r.get_tuning(29)   # items the bucket sort's global path sorted so far (all lanes, sticky)
-    telemetry_after = gpu_telemetry(pci) if rank == 0 else None
-    if F > 1:
+    telemetry_after = gpu_telemetry(pci) if full and rank == 0 else None
+    last_frame = None
+    if args.dump_outputs and rank == 0:
+        # the buffer the timed region's last frame went to, copied before anything renders again
+        if shard.validity:   # per-step gathers: last chunk's last frame, in that chunk's set
+            last = (len(shard.chunks) - 1) % shard.nsets * shard.per_set + shard.chunks[-1][1] - 1
+        else:
+            last = (args.steps - 1) % F if F > 1 else 0
+        last_frame = outs[last].clone()
+    if F > 1 and full:
         # lane 0's blend launches while F frames are in flight: K more frames through the
         # same loop, untimed, with an event pair around every lane-0 blend (a collective at
         # N > 1: every rank runs it)
@@ -737,13 +768,13 @@ def main():
         blend_times_pipe, timed_frames_pipe = r.stage_times()
         r.set_timing(0)
         shard.finish(dev_kind)
-    else:
+    elif full:
         blend_times_pipe, timed_frames_pipe = blend_times, timed_frames
 
     max_elapsed = multi.max_over_ranks(dist, elapsed, "cpu" if gloo else "cuda")
-    max_seq = multi.max_over_ranks(dist, seq_elapsed, "cpu" if gloo else "cuda")
+    max_seq = multi.max_over_ranks(dist, seq_elapsed, "cpu" if gloo else "cuda") if full else None
     scale = None
-    if dist:
+    if dist and full:
         # what each rank renders with no gathers (a short region after the
         # headline, not part of it) and what the gathers cost, so the first SCALE record
         # can be read against DESIGN.md section 8's prediction
@@ -779,12 +810,12 @@ def main():
             dist.destroy_process_group()
         return
 
+    if last_frame is not None:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "image.npy"), last_frame.view(3, H, W).cpu().numpy())
     ms_per_step = max_elapsed / args.steps * 1e3
     value = world * args.steps / max_elapsed
-    blend_avg_ms = blend_times["blend"] / max(1, timed_frames)
-    ntiles = tiles_x * tiles_y
-    bytes_blend = algorithmic_blend_bytes(ntiles, consumed, W, H)
-    achieved = bytes_blend / (blend_avg_ms * 1e-3) / 1e9
     img = outs[0].view(3, H, W)
     result = {
         "metric": ("frames/sec at 1920x1080, 1M Gaussians (config %d%s)"
@@ -816,6 +847,33 @@ def main():
                                + f", {F} frame(s) in flight per GPU (gsr_render_path)",
                    "sh_degree": 3 if args.sh3 else 2, "orbit_step_deg": args.orbit_step,
                    "gaussians": n, "width": W, "height": H, "parallelism": f"frames{world}"},
+        "full": full,
+        "frames_in_flight": F,
+        "depth_bucket_global_items": bucket_over,
+        "image_mean": float(img.mean().item()),
+        "overflow_after_timed": overflow,
+        "overflow_reruns": reruns,
+        "overflow_reruns_unit": "chunks re-rendered and re-gathered inside the timed region (validity words)"
+                                if shard.validity else "timed regions run again (whole region, untimed retry)",
+        "sustained_warmup": {"frames": warm_frames, "min_ms": args.warm_ms},
+    }
+    if gather_ms is not None:
+        result["gather_ms"] = round(gather_ms, 3)
+    if dist:
+        result["scene_broadcast_ms"] = round(broadcast_ms, 2)
+        result["gathers_per_rank_timed"] = shard.gathers
+        result["gather_every"] = args.gather_every
+    if not full:
+        print(json.dumps(result), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
+
+    blend_avg_ms = blend_times["blend"] / max(1, timed_frames)
+    ntiles = tiles_x * tiles_y
+    bytes_blend = algorithmic_blend_bytes(ntiles, consumed, W, H)
+    achieved = bytes_blend / (blend_avg_ms * 1e-3) / 1e9
+    result.update({
         "roofline": {"bound": "hbm", "kernel": BLEND_KERNEL, "achieved": round(achieved, 2),
                      "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                      "traffic": None, "avg_launch_ms": round(blend_avg_ms, 4),
@@ -826,7 +884,6 @@ def main():
                                     "the GPU); avg_launch_ms_inflight = lane 0's launches with F frames in flight "
                                     "(K more frames after the timed regions, an event pair on each)",
                      "avg_launch_ms_inflight": round(blend_times_pipe["blend"] / max(1, timed_frames_pipe), 4)},
-        "frames_in_flight": F,
         "sequential": {"value": round(world * args.steps / max_seq, 3), "unit": "frames/sec",
                        "ms_per_frame": round(max_seq / args.steps * 1e3, 4),
                        "note": "same K frames one at a time on one stream (gsr_render; the viewer's use)"},
@@ -843,28 +900,15 @@ def main():
         "depth_passes": depth_passes,
         "depth_sort": ("bucket sort: stable scatter into depth-quantile buckets + one LDS sort per bucket "
                        "(GSR_TUNE_DEPTH_BUCKETS)" if depth_passes == 0 else f"{depth_passes} LSD radix passes"),
-        "depth_bucket_global_items": bucket_over,
         "pairs_consumed": consumed,
         "blend_exp": {1: "fast (v_exp_f32 alpha, exact alpha tests, guarded T tests, exact re-blend of "
                          "suspect pixels)", 0: "exact (gsr_blend_expf)"}[min(blend_exp, 1)],
         "blend_counters": counters,
         "blend_lane_efficiency": round(counters["active_lanes"] / max(1, counters["lane_slots"]), 4),
-        "image_mean": float(img.mean().item()),
-        "overflow_after_timed": overflow,
-        "overflow_reruns": reruns,
-        "overflow_reruns_unit": "chunks re-rendered and re-gathered inside the timed region (validity words)"
-                                if shard.validity else "timed regions run again (whole region, untimed retry)",
-    }
+    })
     result["gpu_telemetry"] = {"before_warmup": telemetry_before, "after_timed": telemetry_after}
-    result["sustained_warmup"] = {"frames": warm_frames, "min_ms": args.warm_ms}
-    if gather_ms is not None:
-        result["gather_ms"] = round(gather_ms, 3)
     if scale is not None:
         result["scale"] = scale
-    if dist:
-        result["scene_broadcast_ms"] = round(broadcast_ms, 2)
-        result["gathers_per_rank_timed"] = shard.gathers
-        result["gather_every"] = args.gather_every
     sb = algorithmic_stage_bytes(n, visible, pairs, ntiles, consumed, W, H, depth_passes=depth_passes,
                                  row_items=row_items, sh_floats=48 if args.sh3 else 27)
     result["stages_gbs"] = {k: round(sb[k] / (stages[k] * 1e-3) / 1e9, 1) for k in sb if stages.get(k)}

@@ -244,7 +244,7 @@ def test_bench_launches_ranks(gpu, tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "1",
                           "--steps", "6", "--warmup", "2", "--dist-backend", "gloo", "--chunk", "3",
-                          "--scene-dir", str(tmp_path)],
+                          "--scene-dir", str(tmp_path), "--full"],
                          capture_output=True, text=True, timeout=110, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
