@@ -166,11 +166,11 @@ hipError_t launch_bucket_sort(const uint64_t* in, uint64_t* items0, uint64_t* it
 // is empty unless a live item's key saturated to 0xFFFFFFFF), and the row pass then runs
 // with buckets chunks, cstart = totals + buckets (the buckets' first positions) and no count
 // kernel.
-// Big buckets (scenes above 2M Gaussians): `buckets` (kBigBuckets = 512: ~n / 512 items each,
-// sorted by one 1,024-thread workgroup in LDS, up to 16,384 items; or 1,024: ~n / 1,024 items
-// by 512-thread workgroups, up to 8,192, two per CU) bounded by the previous frame's quantiles;
-// larger or wider-keyed buckets are sorted by launch_bucket_sort's local kernel in a second
-// launch.  The scatter writes each tile in bucket order (coalesced 12-B records).
+// Big buckets (scenes above 2M Gaussians): `buckets` must be kBigBuckets (512: ~n / 512 items
+// each, sorted by one 1,024-thread workgroup in LDS, up to 16,384 items) bounded by the
+// previous frame's quantiles; larger or wider-keyed buckets are sorted by launch_bucket_sort's
+// local kernel in a second launch.  The scatter writes each tile in bucket order (coalesced
+// 12-B records).
 // groups <= kBigBucketGroups.  No fused row count.
 constexpr int kBigBuckets = 512;
 constexpr int kBigBucketGroups = 1024;

@@ -26,7 +26,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 
 #include <type_traits>
 
@@ -1745,7 +1744,7 @@ __device__ __forceinline__ void row_range(uint32_t& base, uint32_t& n, const uin
 //                  last is 0xFFFFFFFF, so bucket B - 1 holds exactly the keys equal to
 //                  0xFFFFFFFF: culled items and saturated live keys, which tie)
 //   k_bkt_scan     per bucket, exclusive scan over the chunks (a chunk-major histogram:
-//                  every access a coalesced row segment)
+//                  every access a coalesced row segment); k_bkt_scan_g for the big kind
 //   k_bkt_scatter  stable scatter of the preprocess order into the buckets (per-wave
 //                  returning LDS atomics on packed 16-bit counters, so the rank of an
 //                  item is its order among the wave's earlier items of its bucket);
@@ -1757,6 +1756,11 @@ __device__ __forceinline__ void row_range(uint32_t& base, uint32_t& n, const uin
 //                  capacity is sorted by the same workgroup through global memory
 //                  (stable 8-bit passes ping-ponging with the scratch buffer), so any
 //                  splitters give the exact order; they only set the speed
+// Two kinds ship (gsr_runtime.cpp bkt_big).  Small (up to 2M items, B = 256..4,096 by size):
+// k_bkt_count, k_bkt_scan, the unstaged k_bkt_scatter (16-B records, its own splitter search),
+// k_bkt_local.  Big (above 2M, B = kBigBuckets): k_bkt_count handing each item's bucket on,
+// k_bkt_scan_g, the staged k_bkt_scatter (12-B records), k_bbk_local, then k_bkt_local for the
+// buckets k_bbk_local left.
 // Splitters are the previous frame's quantiles: k_bkt_local writes the key at each
 // bkt_split_pos of the live order for the next frame (double-buffered; the open first and
 // last live buckets a quarter share, the rest even), so the buckets hold about n / B
@@ -1873,11 +1877,11 @@ __global__ __launch_bounds__(kBktThreads) void k_bkt_count(const uint64_t* __res
 // and the bucket's total.  64 buckets per workgroup (one per lane), 16 waves splitting the
 // chunks: every load is a coalesced 256-B row segment.  groups <= kBktMaxGroups.
 constexpr int kBktMaxGroups = kMaxBucketGroups;
-template <int B, int MAXG = kBktMaxGroups>
+template <int B>
 __global__ __launch_bounds__(1024) void k_bkt_scan(uint32_t* __restrict__ hist, int groups,
                                                    uint32_t* __restrict__ totals) {
     GSR_GEOM_PRIO();
-    constexpr int kPerMax = MAXG / 16;
+    constexpr int kPerMax = kBktMaxGroups / 16;
     __shared__ uint32_t s_part[16][64];
     const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
     const uint32_t b = blockIdx.x * 64u + lane;
@@ -1912,48 +1916,16 @@ __global__ __launch_bounds__(1024) void k_bkt_scan(uint32_t* __restrict__ hist, 
     }
 }
 
-// Big buckets (many chunks): one wave per bucket, its lanes splitting the chunks (up to
-// MAXG / 64 each, loads issued together), a wave scan over the lanes.  B / 4 workgroups of
-// four waves: the per-bucket layout of k_bkt_scan put 1.25 MB through 8 workgroups (23 us at
-// 611 chunks).
-template <int B, int MAXG>
-__global__ __launch_bounds__(256) void k_bkt_scan_w(uint32_t* __restrict__ hist, int groups,
-                                                    uint32_t* __restrict__ totals) {
-    GSR_GEOM_PRIO();
-    constexpr int kPerMax = MAXG / 64;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t b = blockIdx.x * 4u + (threadIdx.x >> 6);
-    const uint32_t per = ((uint32_t)groups + 63u) / 64u;
-    const uint32_t g0 = lane * per;
-    uint32_t v[kPerMax], sum = 0;
-#pragma unroll
-    for (int i = 0; i < kPerMax; i++) {
-        const uint32_t g = g0 + (uint32_t)i;
-        v[i] = (uint32_t)i < per && g < (uint32_t)groups ? hist[(size_t)g * B + b] : 0u;
-        sum += v[i];
-    }
-    const uint32_t incl = wave_incl_scan(sum, OpAdd{});
-    uint32_t run = incl - sum;
-    if (lane == 63) totals[b] = incl;
-    if (b == 0 && lane == 0) totals[2 * B + 1] = 0u;   // bkt_sat_word (as k_bkt_scan)
-#pragma unroll
-    for (int i = 0; i < kPerMax; i++) {
-        const uint32_t g = g0 + (uint32_t)i;
-        if ((uint32_t)i < per && g < (uint32_t)groups) {
-            hist[(size_t)g * B + b] = run;
-            run += v[i];
-        }
-    }
-}
-
-// Big buckets (A/B, GSR_BB_SCANG=1): 16 buckets per 1,024-thread workgroup, each wave's four
-// 16-lane quarters reading a 64-B row segment of four different chunks (64 chunk slices per
-// workgroup), the slices' sums combined in LDS.  B / 16 workgroups.
-template <int B, int MAXG>
+// The big buckets' scan (kBigBuckets buckets, up to kBigBucketGroups chunks: k_bkt_scan's
+// layout put 1.25 MB through 8 workgroups, 23 us at 611 chunks): 16 buckets per 1,024-thread
+// workgroup, each wave's four 16-lane quarters reading a 64-B row segment of four different
+// chunks (64 chunk slices per workgroup), the slices' sums combined in LDS.  B / 16
+// workgroups.  (A wave per bucket measured 8.5 against 5.9 us)
 __global__ __launch_bounds__(1024) void k_bkt_scan_g(uint32_t* __restrict__ hist, int groups,
                                                      uint32_t* __restrict__ totals) {
     GSR_GEOM_PRIO();
-    constexpr int kPerMax = (MAXG + 63) / 64;
+    constexpr int B = kBigBuckets;
+    constexpr int kPerMax = (kBigBucketGroups + 63) / 64;
     __shared__ uint32_t s_part[64][16];
     const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
     const uint32_t bl = lane & 15u, sl = w * 4u + (lane >> 4);   // bucket in the group, chunk slice
@@ -2023,13 +1995,18 @@ __device__ __forceinline__ void rec_put(uint4* __restrict__ rec, uint32_t q, uin
 // back contiguously.  The last bucket (key 0xFFFFFFFF, never sorted) goes straight to its
 // final place in out / pay_out.  The next tile's items and rects are loaded while this one
 // is ranked.
-// STAGE: the tile is laid out in LDS by bucket first (tile-local position = the bucket's
-// offset in the tile + the item's stable rank in it), then written out by position, so the
-// lanes of a store that hold items of one bucket write consecutive records (a run per bucket
-// and tile: ~4 items at 512 buckets) instead of one store request each.
-template <int B, bool RA, int TH, bool STAGE = false, uint32_t TILE = kBktTile, int WPE = 1, bool R12 = false,
-          bool LEAN = false, bool BID = false>
-__global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu(WPE))) void k_bkt_scatter(const uint64_t* __restrict__ in,
+// STAGED (the big buckets' scatter): the tile is laid out in LDS by bucket first (tile-local
+// position = the bucket's offset in the tile + the item's stable rank in it), then written out
+// by position, so the lanes of a store that hold items of one bucket write consecutive 12-B
+// records (a run per bucket and tile: ~4 items at 512 buckets) instead of one store request
+// each.  It takes every item's bucket from the count kernel (bid) instead of searching the
+// splitters again, and thread t < B / 2 owns counter word t (buckets 2t, 2t + 1), so the
+// word's wave prefix and the tile offsets' scan are one step; the counters are cleared for the
+// next tile after their last read (the stage writes), so a tile starts without a clear +
+// barrier: five barriers per tile.  Unstaged (the small kind): the scatter searches the
+// splitters itself and writes one 16-B record per item straight from registers.
+template <int B, bool RA, int TH, bool STAGED>
+__global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu(1))) void k_bkt_scatter(const uint64_t* __restrict__ in,
                                                              uint64_t* __restrict__ out, uint32_t n,
                                                              const uint32_t* __restrict__ splitters, int groups,
                                                              const uint32_t* __restrict__ hist,
@@ -2040,23 +2017,19 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu(WPE))) void 
                                                              uint4* __restrict__ rec,
                                                              const uint16_t* __restrict__ bid) {
     GSR_GEOM_PRIO();
+    constexpr uint32_t TILE = kBktTile;
     constexpr int NW = TH / 64, kIt = TILE / TH;  // waves; items per thread
     constexpr uint32_t kW = B / 2;                      // packed counter words per wave
     constexpr int kPer = B / TH;                        // buckets per thread (scan)
     constexpr int kWPer = (kW + TH - 1) / TH;           // counter words per thread
-    static_assert(kPer >= 1 && kIt * TH == TILE && TILE % kBktTile == 0, "bucket / thread split");
-    // LEAN (staged, one counter word per thread): thread t < kW owns word t (buckets 2t, 2t + 1),
-    // so its wave prefix and the tile offsets' scan are one step (no s_tc, one barrier fewer);
-    // the scan keeps only its first barrier, and the counters are cleared for the next tile
-    // after their last read (the stage writes), so the tile starts without a clear + barrier:
-    // five barriers per tile instead of eight
-    constexpr bool kLean = LEAN && STAGE && kW <= (uint32_t)TH;
+    static_assert(kPer >= 1 && kIt * TH == TILE, "bucket / thread split");
+    static_assert(!STAGED || B / 2 <= TH, "staged: one counter word per thread");
     __shared__ uint32_t s_S[B], s_gbase[B];
     __shared__ uint32_t s_wc[NW][kW];
     __shared__ uint32_t s_scr[NW];
-    // STAGE: per-word tile counts, per-bucket tile offsets, the tile in bucket order
-    __shared__ uint32_t s_tc[STAGE ? kW : 1], s_tp[STAGE ? B : 1];
-    __shared__ uint4 s_stage[STAGE ? TILE : 1];
+    // STAGED: per-bucket tile offsets, the tile in bucket order
+    __shared__ uint32_t s_tp[STAGED ? B : 1];
+    __shared__ uint4 s_stage[STAGED ? TILE : 1];
     const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
     const uint64_t lt_mask = lane == 0 ? 0ull : (~0ull >> (64 - lane));
     const int chunk = xcd_chunk((int)blockIdx.x, groups);   // each XCD takes a contiguous run of chunks
@@ -2065,20 +2038,20 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu(WPE))) void 
     const uint32_t wbase = w * 64 * kIt;
     uint64_t it[kIt];
     uint32_t pv[kIt], bv[kIt];
-    // BID: the count kernel's bucket of every item (bid), loaded with the tile
+    // STAGED: the count kernel's bucket of every item (bid), loaded with the tile
     auto load = [&](uint64_t tb, uint32_t tn, uint64_t (&ii)[kIt], uint32_t (&pp)[kIt], uint32_t (&bb)[kIt]) {
 #pragma unroll
         for (int k = 0; k < kIt; k++) {
             const uint32_t el = wbase + k * 64 + lane;
             ii[k] = el < tn ? in[tb + el] : ~0ull;
             pp[k] = el < tn ? rect[tb + el] : 0u;   // the input is the preprocess order: rect by position
-            if (BID) bb[k] = el < tn ? (uint32_t)bid[tb + el] : (uint32_t)B - 1u;
+            if (STAGED) bb[k] = el < tn ? (uint32_t)bid[tb + el] : (uint32_t)B - 1u;
         }
     };
     // the first tile's items and rects, the splitters, the bucket totals and this chunk's
     // histogram row are all loaded in one memory round trip
     load(b, (uint32_t)min((uint64_t)TILE, e - b), it, pv, bv);
-    if (!BID) bkt_load_splitters<B, TH>(s_S, splitters);
+    if (!STAGED) bkt_load_splitters<B, TH>(s_S, splitters);
     {   // this chunk's first slot in every bucket: the bucket's start + the earlier chunks' items
         uint32_t loc[kPer], hrow[kPer], sum = 0;
 #pragma unroll
@@ -2099,7 +2072,7 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu(WPE))) void 
         if (chunk == 0 && t == 0) bstart[B] = n;
     }
     if (b >= e) return;   // uniform per workgroup, after the scan's barriers
-    if (kLean) {
+    if (STAGED) {   // the first tile's counter clear; every later one follows the stage writes
         for (uint32_t j = t; j < NW * kW; j += TH) (&s_wc[0][0])[j] = 0;
         __syncthreads();
     }
@@ -2109,14 +2082,14 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu(WPE))) void 
         uint64_t nit[kIt];
         uint32_t npv[kIt], nbv[kIt];
         if (more) load(tb + TILE, (uint32_t)min((uint64_t)TILE, e - tb - TILE), nit, npv, nbv);
-        if (!kLean) {
+        if (!STAGED) {
             for (uint32_t j = t; j < NW * kW; j += TH) (&s_wc[0][0])[j] = 0;
             __syncthreads();
         }
         uint32_t dg[kIt], rk[kIt], keys[kIt];
 #pragma unroll
         for (int k = 0; k < kIt; k++) keys[k] = (uint32_t)(it[k] >> 32);
-        if (BID) {
+        if (STAGED) {
 #pragma unroll
             for (int k = 0; k < kIt; k++) dg[k] = bv[k];
         } else {
@@ -2179,10 +2152,9 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu(WPE))) void 
                     run += c[v];
                 }
                 tc[q] = run;
-                if (STAGE && !kLean) s_tc[j] = run;
             }
         }
-        if (kLean) {
+        if (STAGED) {
             // the buckets' offsets in the tile: thread t < kW scans word t's two tile counts
             const uint32_t lo = tc[0] & 0xffffu, hi = tc[0] >> 16;
             uint32_t tot;
@@ -2191,30 +2163,9 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu(WPE))) void 
                 s_tp[2 * t] = ex;
                 s_tp[2 * t + 1] = ex + lo;
             }
-            __syncthreads();
-        } else {
-            __syncthreads();
         }
-        if (STAGE && !kLean) {
-            // the buckets' offsets in the tile: exclusive scan of their tile counts (thread t
-            // owns buckets t * kPer .. + kPer - 1)
-            uint32_t c[kPer], sum = 0;
-#pragma unroll
-            for (int k = 0; k < kPer; k++) {
-                const uint32_t d = t * kPer + k;
-                c[k] = half16(s_tc[d >> 1], d & 1u);
-                sum += c[k];
-            }
-            uint32_t tot;
-            uint32_t run = block_exclusive_scan<uint32_t, NW>(sum, s_scr, tot);
-#pragma unroll
-            for (int k = 0; k < kPer; k++) {
-                s_tp[t * kPer + k] = run;
-                run += c[k];
-            }
-            __syncthreads();
-        }
-        if (STAGE) {
+        __syncthreads();
+        if (STAGED) {
 #pragma unroll
             for (int k = 0; k < kIt; k++) {
                 const uint32_t el = wbase + k * 64 + lane;
@@ -2225,8 +2176,8 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu(WPE))) void 
                 }
             }
             __syncthreads();
-            if (kLean)   // the counters' last read is behind: clear them for the next tile
-                for (uint32_t j = t; j < NW * kW; j += TH) (&s_wc[0][0])[j] = 0;
+            // the counters' last read is behind: clear them for the next tile
+            for (uint32_t j = t; j < NW * kW; j += TH) (&s_wc[0][0])[j] = 0;
             for (uint32_t q = t; q < tn; q += TH) {
                 const uint4 r = s_stage[q];
                 const uint32_t d = r.w;
@@ -2235,7 +2186,7 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu(WPE))) void 
                     out[dst] = ((uint64_t)r.y << 32) | r.x;
                     pay_out[dst] = r.z;
                 } else {
-                    rec_put<R12>(rec, dst, r.x, r.y, r.z);
+                    rec_put<true>(rec, dst, r.x, r.y, r.z);
                 }
             }
         } else {
@@ -2249,7 +2200,7 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu(WPE))) void 
                         out[dst] = it[k];
                         pay_out[dst] = pv[k];
                     } else {
-                        rec_put<R12>(rec, dst, (uint32_t)it[k], (uint32_t)(it[k] >> 32), pv[k]);
+                        rec_put<false>(rec, dst, (uint32_t)it[k], (uint32_t)(it[k] >> 32), pv[k]);
                     }
                 }
             }
@@ -2259,7 +2210,7 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu(WPE))) void 
             for (int k = 0; k < kIt; k++) {
                 it[k] = nit[k];
                 pv[k] = npv[k];
-                if (BID) bv[k] = nbv[k];
+                if (STAGED) bv[k] = nbv[k];
             }
         }
         __syncthreads();
@@ -2271,7 +2222,8 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu(WPE))) void 
                 s_gbase[2 * j + 1] += tc[q] >> 16;
             }
         }
-        // the next tile's counter reset + barrier orders these updates before their use
+        // the next tile's barrier after the ranking atomics (STAGED), or its counter clear and
+        // barrier (unstaged), orders these updates before their use
     }
 }
 
@@ -2647,16 +2599,17 @@ __global__ __launch_bounds__(kBktThreads) void k_bkt_local(uint64_t* __restrict_
 // out coalesced.  Buckets over the capacity or wider than 18 bits are flagged in `left` and
 // sorted by k_bkt_local's paths in a second launch.
 constexpr int kBbThreads = 1024;
-constexpr int kBbItems = 16;                            // capacity TH * 16: 16,384 at 1,024 threads
+constexpr int kBbItems = 16;                            // capacity kBbThreads * 16: 16,384
 
-// TH threads (1,024: capacity 16,384, one workgroup per CU; 512: 8,192 at half the LDS)
-template <int B, bool RA, bool R12, int TH = kBbThreads>
-__global__ __launch_bounds__(TH) void k_bbk_local(uint64_t* __restrict__ items, uint32_t* __restrict__ pay,
-                                                  const uint32_t* __restrict__ bstart,
-                                                  const uint32_t* __restrict__ s_in,
-                                                  uint32_t* __restrict__ s_next, uint32_t cap,
-                                                  const uint4* __restrict__ rec, uint32_t* __restrict__ left) {
+// One workgroup per CU; it reads the staged scatter's 12-B records.
+template <bool RA>
+__global__ __launch_bounds__(kBbThreads) void k_bbk_local(uint64_t* __restrict__ items, uint32_t* __restrict__ pay,
+                                                          const uint32_t* __restrict__ bstart,
+                                                          const uint32_t* __restrict__ s_in,
+                                                          uint32_t* __restrict__ s_next, uint32_t cap,
+                                                          const uint4* __restrict__ rec, uint32_t* __restrict__ left) {
     GSR_GEOM_PRIO();
+    constexpr int B = kBigBuckets, TH = kBbThreads;
     constexpr int NW = TH / 64;
     constexpr uint32_t kCap = (uint32_t)TH * kBbItems;
     constexpr int kBbSlot = __builtin_ctz(kCap);        // slot bits of the exchange word
@@ -2693,7 +2646,7 @@ __global__ __launch_bounds__(TH) void k_bbk_local(uint64_t* __restrict__ items, 
         for (int k = 0; k < kBbItems; k++) {
             const uint32_t el = wbase + k * 64 + lane;
             const bool in = k < (int)kk && el < count;
-            const uint4 r = in ? rec_get<R12>(rec, start + el) : make_uint4(0u, 0xffffffffu, 0u, 0u);
+            const uint4 r = in ? rec_get<true>(rec, start + el) : make_uint4(0u, 0xffffffffu, 0u, 0u);
             if (in) s_idx[el] = r.x;
             key[k] = r.y;
             rct[k] = r.z;
@@ -4331,6 +4284,13 @@ __global__ void k_xs_probe(const float* __restrict__ op, int n, float* __restric
     if (i < n) out[i] = gsr_alpha_take_min_x(op[i]);
 }
 
+// f(std::true_type{}) or f(std::false_type{}): a runtime bool as a template argument of the
+// launches in the generic lambda f.
+template <typename F>
+inline auto with_bool(bool b, F&& f) {
+    return b ? f(std::true_type{}) : f(std::false_type{});
+}
+
 inline int grid_for(int64_t n, int block) { return (int)((n + block - 1) / block); }
 
 }  // namespace
@@ -4375,26 +4335,20 @@ static void radix_pass(const uint64_t* in, uint64_t* out, const uint32_t* n_dev,
                        int pass, const uint32_t* rect, int rect_direct, uint32_t* pay0, uint32_t* pay1,
                        hipStream_t s, SortRange sr) {
     const uint32_t mask = (1u << bits) - 1u;
-    if (sr.filter)
-        hipLaunchKernelGGL((k_radix_upsweep<ITEMS, true>), dim3(groups), dim3(kSortThreads), 0, s, in, n_dev, n_host,
-                           shift, mask, groups, hist, dstats, pass, sr);
-    else
-        hipLaunchKernelGGL((k_radix_upsweep<ITEMS, false>), dim3(groups), dim3(kSortThreads), 0, s, in, n_dev, n_host,
-                           shift, mask, groups, hist, dstats, pass, sr);
-    hipLaunchKernelGGL(k_radix_scan, dim3(256), dim3(256), 0, s, hist, groups, totals,
-                       static_cast<const uint32_t*>(dstats), pass, sr.gate);
     // rect payloads (binning): pass p reads pay[p & 1] (pass 0: rect, or pay[0] when
     // rect_direct < 0 — the live partition wrote it) and writes pay[(p + 1) & 1]
     const uint32_t* pay_in = pay0 && (pass > 0 || rect_direct < 0) ? ((pass & 1) ? pay1 : pay0) : nullptr;
     uint32_t* pay_out = pay0 ? ((pass & 1) ? pay0 : pay1) : nullptr;
-    if (sr.filter)
-        hipLaunchKernelGGL((k_radix_downsweep<ITEMS, RA, true>), dim3(groups), dim3(kSortThreads), 0, s, in, out, n_dev,
+    with_bool(sr.filter != 0, [&](auto filt) {
+        constexpr bool FILT = decltype(filt)::value;
+        hipLaunchKernelGGL((k_radix_upsweep<ITEMS, FILT>), dim3(groups), dim3(kSortThreads), 0, s, in, n_dev, n_host,
+                           shift, mask, groups, hist, dstats, pass, sr);
+        hipLaunchKernelGGL(k_radix_scan, dim3(256), dim3(256), 0, s, hist, groups, totals,
+                           static_cast<const uint32_t*>(dstats), pass, sr.gate);
+        hipLaunchKernelGGL((k_radix_downsweep<ITEMS, RA, FILT>), dim3(groups), dim3(kSortThreads), 0, s, in, out, n_dev,
                            n_host, shift, bits, groups, hist, totals, ranges, static_cast<const uint32_t*>(dstats), pass,
                            rect, rect_direct > 0 ? 1 : 0, pay_in, pay_out, sr);
-    else
-        hipLaunchKernelGGL((k_radix_downsweep<ITEMS, RA, false>), dim3(groups), dim3(kSortThreads), 0, s, in, out, n_dev,
-                           n_host, shift, bits, groups, hist, totals, ranges, static_cast<const uint32_t*>(dstats), pass,
-                           rect, rect_direct > 0 ? 1 : 0, pay_in, pay_out, sr);
+    });
 }
 
 hipError_t launch_radix_pass(const uint64_t* in, uint64_t* out, const uint32_t* n_dev, uint32_t n_host,
@@ -4415,18 +4369,16 @@ hipError_t launch_radix_pass(const uint64_t* in, uint64_t* out, const uint32_t* 
     // 16 items per thread always rank with ballots, one tile per workgroup
     // (k_radix_downsweep): a grid too small for that sorts 8 per thread
     if (items == 16 && (uint64_t)groups * kSortTile < (uint64_t)n_host) items = 8;
-    if (items == 4 && rank_atomic)
-        radix_pass<4, true>(in, out, n_dev, n_host, shift, bits, groups, hist, totals, ranges, dstats, pass, rect,
-                            rect_direct, pay0, pay1, s, sr);
-    else if (items == 4)
-        radix_pass<4, false>(in, out, n_dev, n_host, shift, bits, groups, hist, totals, ranges, dstats, pass, rect,
-                             rect_direct, pay0, pay1, s, sr);
-    else if (items == 8 && rank_atomic)
-        radix_pass<8, true>(in, out, n_dev, n_host, shift, bits, groups, hist, totals, ranges, dstats, pass, rect,
-                            rect_direct, pay0, pay1, s, sr);
-    else if (items == 8)
-        radix_pass<8, false>(in, out, n_dev, n_host, shift, bits, groups, hist, totals, ranges, dstats, pass, rect,
-                             rect_direct, pay0, pay1, s, sr);
+    if (items == 4 || items == 8)
+        with_bool(rank_atomic, [&](auto ra) {
+            constexpr bool RA = decltype(ra)::value;
+            if (items == 4)
+                radix_pass<4, RA>(in, out, n_dev, n_host, shift, bits, groups, hist, totals, ranges, dstats, pass, rect,
+                                  rect_direct, pay0, pay1, s, sr);
+            else
+                radix_pass<8, RA>(in, out, n_dev, n_host, shift, bits, groups, hist, totals, ranges, dstats, pass, rect,
+                                  rect_direct, pay0, pay1, s, sr);
+        });
     else
         radix_pass<16, false>(in, out, n_dev, n_host, shift, bits, groups, hist, totals, ranges, dstats, pass, rect,
                               rect_direct, pay0, pay1, s, sr);
@@ -4444,79 +4396,17 @@ static void bucket_sort_b(const uint64_t* in, uint64_t* items0, uint64_t* items1
     const int local_grid = row_tiles_y > 0 ? B : B - 1;
     uint32_t* bstart = totals + B;   // B + 2 words after the totals
     constexpr int kScTh = B >= 512 ? 512 : kBktThreads;   // k_bkt_scatter's workgroup size
-    // A/B: GSR_BKT_SCATTER_256=1 runs the 4,096-bucket scatter in 256-thread workgroups (64 KB of
-    // LDS instead of 96: two workgroups per CU)
-    static const bool sc256 = [] { const char* e = std::getenv("GSR_BKT_SCATTER_256"); return e && e[0] == '1'; }();
-    // A/B: GSR_BKT_STAGE_SMALL=1 writes each scatter tile in bucket order here too
-    static const bool stage = [] { const char* e = std::getenv("GSR_BKT_STAGE_SMALL"); return e && e[0] == '1'; }();
-    // A/B: GSR_BKT_BID=1 hands each item's bucket from the count to the scatter (big buckets' scheme)
-    static const bool bids = [] { const char* e = std::getenv("GSR_BKT_BID"); return e && e[0] == '1'; }();
-    const bool bid_on = bids && !stage && !(B == 4096 && sc256);
-    uint16_t* bid = bid_on ? reinterpret_cast<uint16_t*>(pay1) : nullptr;
-    hipLaunchKernelGGL(k_bkt_count<B>, dim3(groups), dim3(kBktThreads), 0, s, in, n, s_in, groups, hist, bid);
-    // A/B: GSR_BKT_SCANG=1 scans 16 buckets per workgroup over 64 chunk slices (the big buckets' scan)
-    static const bool scang = [] { const char* e = std::getenv("GSR_BKT_SCANG"); return e && e[0] == '1'; }();
-    if (scang)
-        hipLaunchKernelGGL((k_bkt_scan_g<B, kBktMaxGroups>), dim3(B / 16), dim3(1024), 0, s, hist, groups, totals);
-    else
-        hipLaunchKernelGGL(k_bkt_scan<B>, dim3(B / 64), dim3(1024), 0, s, hist, groups, totals);
-    if (stage) {
-        auto run = [&](auto ra) {
-            constexpr bool RA = decltype(ra)::value;
-            hipLaunchKernelGGL((k_bkt_scatter<B, RA, kScTh, true>), dim3(groups), dim3(kScTh), 0, s, in, items0, n,
-                               s_in, groups, hist, static_cast<const uint32_t*>(totals), rect, pay0, bstart, rec,
-                               static_cast<const uint16_t*>(nullptr));
-            hipLaunchKernelGGL((k_bkt_local<B, RA>), dim3(local_grid), dim3(kBktThreads), 0, s, items0, items1, pay0,
-                               pay1, bstart, s_in, s_out, cap, over_host, rh, static_cast<const uint4*>(rec));
-        };
-        if (rank_atomic) run(std::true_type{});
-        else run(std::false_type{});
-        return;
-    }
-    if (B == 4096 && sc256) {
-        if (rank_atomic)
-            hipLaunchKernelGGL((k_bkt_scatter<B, true, kBktThreads>), dim3(groups), dim3(kBktThreads), 0, s, in, items0,
-                               n, s_in, groups, hist, static_cast<const uint32_t*>(totals), rect, pay0, bstart, rec,
-                               static_cast<const uint16_t*>(nullptr));
-        else
-            hipLaunchKernelGGL((k_bkt_scatter<B, false, kBktThreads>), dim3(groups), dim3(kBktThreads), 0, s, in, items0,
-                               n, s_in, groups, hist, static_cast<const uint32_t*>(totals), rect, pay0, bstart, rec,
-                               static_cast<const uint16_t*>(nullptr));
-        if (rank_atomic)
-            hipLaunchKernelGGL((k_bkt_local<B, true>), dim3(local_grid), dim3(kBktThreads), 0, s, items0, items1, pay0,
-                               pay1, bstart, s_in, s_out, cap, over_host, rh, static_cast<const uint4*>(rec));
-        else
-            hipLaunchKernelGGL((k_bkt_local<B, false>), dim3(local_grid), dim3(kBktThreads), 0, s, items0, items1, pay0,
-                               pay1, bstart, s_in, s_out, cap, over_host, rh, static_cast<const uint4*>(rec));
-        return;
-    }
-    if (bid_on) {
-        auto run = [&](auto ra) {
-            constexpr bool RA = decltype(ra)::value;
-            hipLaunchKernelGGL((k_bkt_scatter<B, RA, kScTh, false, kBktTile, 1, false, false, true>), dim3(groups),
-                               dim3(kScTh), 0, s, in, items0, n, s_in, groups, hist,
-                               static_cast<const uint32_t*>(totals), rect, pay0, bstart, rec,
-                               static_cast<const uint16_t*>(bid));
-            hipLaunchKernelGGL((k_bkt_local<B, RA>), dim3(local_grid), dim3(kBktThreads), 0, s, items0, items1, pay0,
-                               pay1, bstart, s_in, s_out, cap, over_host, rh, static_cast<const uint4*>(rec));
-        };
-        if (rank_atomic) run(std::true_type{});
-        else run(std::false_type{});
-        return;
-    }
-    if (rank_atomic) {
-        hipLaunchKernelGGL((k_bkt_scatter<B, true, kScTh>), dim3(groups), dim3(kScTh), 0, s, in, items0, n, s_in,
+    hipLaunchKernelGGL(k_bkt_count<B>, dim3(groups), dim3(kBktThreads), 0, s, in, n, s_in, groups, hist,
+                       static_cast<uint16_t*>(nullptr));
+    hipLaunchKernelGGL(k_bkt_scan<B>, dim3(B / 64), dim3(1024), 0, s, hist, groups, totals);
+    with_bool(rank_atomic, [&](auto ra) {
+        constexpr bool RA = decltype(ra)::value;
+        hipLaunchKernelGGL((k_bkt_scatter<B, RA, kScTh, false>), dim3(groups), dim3(kScTh), 0, s, in, items0, n, s_in,
                            groups, hist, static_cast<const uint32_t*>(totals), rect, pay0, bstart, rec,
-                               static_cast<const uint16_t*>(nullptr));
-        hipLaunchKernelGGL((k_bkt_local<B, true>), dim3(local_grid), dim3(kBktThreads), 0, s, items0, items1, pay0,
+                           static_cast<const uint16_t*>(nullptr));
+        hipLaunchKernelGGL((k_bkt_local<B, RA>), dim3(local_grid), dim3(kBktThreads), 0, s, items0, items1, pay0,
                            pay1, bstart, s_in, s_out, cap, over_host, rh, static_cast<const uint4*>(rec));
-    } else {
-        hipLaunchKernelGGL((k_bkt_scatter<B, false, kScTh>), dim3(groups), dim3(kScTh), 0, s, in, items0, n, s_in,
-                           groups, hist, static_cast<const uint32_t*>(totals), rect, pay0, bstart, rec,
-                               static_cast<const uint16_t*>(nullptr));
-        hipLaunchKernelGGL((k_bkt_local<B, false>), dim3(local_grid), dim3(kBktThreads), 0, s, items0, items1, pay0,
-                           pay1, bstart, s_in, s_out, cap, over_host, rh, static_cast<const uint4*>(rec));
-    }
+    });
 }
 
 hipError_t launch_bucket_sort(const uint64_t* in, uint64_t* items0, uint64_t* items1, uint32_t n, int buckets,
@@ -4540,66 +4430,40 @@ hipError_t launch_bucket_sort(const uint64_t* in, uint64_t* items0, uint64_t* it
     return hipGetLastError();
 }
 
-// B buckets, sorted by TH-thread workgroups (512 / 1,024 or 1,024 / 512).  The scatter's tile
-// is staged (bucket runs written coalesced), barrier-lean (52.0 -> 50.2 us at config 3 orbit)
-// and writes 12-B records (16-B: 51.7 -> 50.5 us); the eight-barrier tile, 16-B records and
-// the unstaged scatter measured slower (profiles/r06k_big_buckets_c3_orbit.txt, DESIGN.md
+// kBigBuckets buckets, each sorted by one kBbThreads-thread workgroup.  The scatter's tile is
+// staged (bucket runs written coalesced), barrier-lean (52.0 -> 50.2 us at config 3 orbit) and
+// writes 12-B records (16-B: 51.7 -> 50.5 us); the eight-barrier tile, 16-B records and the
+// unstaged scatter measured slower (profiles/r06k_big_buckets_c3_orbit.txt, DESIGN.md
 // section 3).
-template <int B, int TH>
-static void bucket_sort_big_b(const uint64_t* in, uint64_t* items0, uint64_t* items1, uint32_t n, int groups,
-                              const uint32_t* s_in, uint32_t* s_out, uint32_t* hist, uint32_t* totals,
-                              const uint32_t* rect, uint32_t* pay0, uint32_t* pay1, bool rank_atomic, uint32_t cap,
-                              unsigned int* over_host, hipStream_t s, uint4* rec) {
-    uint32_t* bstart = totals + B;          // B + 2 words after the totals
-    uint32_t* left = totals + 2 * B + 2;    // per bucket: k_bbk_local left it to k_bkt_local
-    const RowHist none{nullptr, B, 0};
-    // the count hands each item's bucket to the scatter (u16 in pay1, free until the second
-    // launch), which then skips its own splitter search (GSR_BB_BID=0: it searches, A/B)
-    static const bool bids = [] { const char* e = std::getenv("GSR_BB_BID"); return !e || e[0] != '0'; }();
-    uint16_t* bid = bids ? reinterpret_cast<uint16_t*>(pay1) : nullptr;
-    hipLaunchKernelGGL(k_bkt_count<B>, dim3(groups), dim3(kBktThreads), 0, s, in, n, s_in, groups, hist, bid);
-    // chunk scan: 16 buckets per workgroup over 64 chunk slices (5.9 vs 8.5 us for a wave per
-    // bucket at config 3, profiles/r06sg_kt_big_bucket_scan.txt); GSR_BB_SCANG=0 for the latter
-    static const bool scang = [] { const char* e = std::getenv("GSR_BB_SCANG"); return !e || e[0] != '0'; }();
-    if (scang)
-        hipLaunchKernelGGL((k_bkt_scan_g<B, kBigBucketGroups>), dim3(B / 16), dim3(1024), 0, s, hist, groups, totals);
-    else
-        hipLaunchKernelGGL((k_bkt_scan_w<B, kBigBucketGroups>), dim3(B / 4), dim3(256), 0, s, hist, groups, totals);
-    auto run = [&](auto ra) {
-        constexpr bool RA = decltype(ra)::value;
-        if (bids)
-            hipLaunchKernelGGL((k_bkt_scatter<B, RA, 512, true, kBktTile, 1, true, true, true>), dim3(groups), dim3(512),
-                               0, s, in, items0, n, s_in, groups, hist, static_cast<const uint32_t*>(totals), rect,
-                               pay0, bstart, rec, static_cast<const uint16_t*>(bid));
-        else
-            hipLaunchKernelGGL((k_bkt_scatter<B, RA, 512, true, kBktTile, 1, true, true>), dim3(groups), dim3(512), 0,
-                               s, in, items0, n, s_in, groups, hist, static_cast<const uint32_t*>(totals), rect, pay0,
-                               bstart, rec, static_cast<const uint16_t*>(nullptr));
-        hipLaunchKernelGGL((k_bbk_local<B, RA, true, TH>), dim3(B - 1), dim3(TH), 0, s, items0, pay0,
-                           static_cast<const uint32_t*>(bstart), s_in, s_out, cap, static_cast<const uint4*>(rec), left);
-        hipLaunchKernelGGL((k_bkt_local<B, RA, true>), dim3(B - 1), dim3(kBktThreads), 0, s, items0, items1, pay0,
-                           pay1, bstart, s_in, s_out, min(cap, kBktCap), over_host, none,
-                           static_cast<const uint4*>(rec), static_cast<const uint32_t*>(left));
-    };
-    if (rank_atomic) run(std::true_type{});
-    else run(std::false_type{});
-}
-
 hipError_t launch_bucket_sort_big(const uint64_t* in, uint64_t* items0, uint64_t* items1, uint32_t n, int buckets,
                                   int groups, const uint32_t* s_in, uint32_t* s_out, uint32_t* hist, uint32_t* totals,
                                   const uint32_t* rect, uint32_t* pay0, uint32_t* pay1, bool rank_atomic, uint32_t cap,
                                   unsigned int* over_host, hipStream_t s, uint4* rec) {
-    if ((buckets != 512 && buckets != 1024) || groups < 1 || groups > kBigBucketGroups ||
+    constexpr int B = kBigBuckets;
+    if (buckets != B || groups < 1 || groups > kBigBucketGroups ||
         (int64_t)groups * buckets > 256 * (int64_t)kMaxSortGroups || cap < 1 || in == items0 || !rect || !pay0 ||
         !pay1 || !rec)
         return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
-    if (buckets == 512)
-        bucket_sort_big_b<512, 1024>(in, items0, items1, n, groups, s_in, s_out, hist, totals, rect, pay0, pay1,
-                                     rank_atomic, cap, over_host, s, rec);
-    else
-        bucket_sort_big_b<1024, 512>(in, items0, items1, n, groups, s_in, s_out, hist, totals, rect, pay0, pay1,
-                                     rank_atomic, cap, over_host, s, rec);
+    uint32_t* bstart = totals + B;          // B + 2 words after the totals
+    uint32_t* left = totals + 2 * B + 2;    // per bucket: k_bbk_local left it to k_bkt_local
+    const RowHist none{nullptr, B, 0};
+    // the count hands each item's bucket to the scatter (u16 in pay1, free until the second
+    // launch), which then skips its own splitter search
+    uint16_t* bid = reinterpret_cast<uint16_t*>(pay1);
+    hipLaunchKernelGGL(k_bkt_count<B>, dim3(groups), dim3(kBktThreads), 0, s, in, n, s_in, groups, hist, bid);
+    hipLaunchKernelGGL(k_bkt_scan_g, dim3(B / 16), dim3(1024), 0, s, hist, groups, totals);
+    with_bool(rank_atomic, [&](auto ra) {
+        constexpr bool RA = decltype(ra)::value;
+        hipLaunchKernelGGL((k_bkt_scatter<B, RA, 512, true>), dim3(groups), dim3(512), 0, s, in, items0, n, s_in,
+                           groups, hist, static_cast<const uint32_t*>(totals), rect, pay0, bstart, rec,
+                           static_cast<const uint16_t*>(bid));
+        hipLaunchKernelGGL(k_bbk_local<RA>, dim3(B - 1), dim3(kBbThreads), 0, s, items0, pay0,
+                           static_cast<const uint32_t*>(bstart), s_in, s_out, cap, static_cast<const uint4*>(rec), left);
+        hipLaunchKernelGGL((k_bkt_local<B, RA, true>), dim3(B - 1), dim3(kBktThreads), 0, s, items0, items1, pay0,
+                           pay1, bstart, s_in, s_out, min(cap, kBktCap), over_host, none,
+                           static_cast<const uint4*>(rec), static_cast<const uint32_t*>(left));
+    });
     return hipGetLastError();
 }
 
@@ -4663,14 +4527,13 @@ hipError_t launch_bin_rows(const uint64_t* items0, const uint64_t* items1, const
                            hist, base, g, cut, cut_mode, cut_n);
     hipLaunchKernelGGL(k_bin_rows_scan, dim3(256), dim3(256), 0, s, hist, groups, tiles_y, row_items, row_pairs,
                        gate, gate_mode);
-    auto pick = [&](auto ra) {
+    auto scatter = with_bool(rank_atomic, [&](auto ra) {
         constexpr bool RA = decltype(ra)::value;
         return tiles_y <= 128 ? (items == 4 ? k_bin_rows_scatter<4, 7, RA> : items == 8 ? k_bin_rows_scatter<8, 7, RA>
                                                                                      : k_bin_rows_scatter<16, 7, RA>)
                               : (items == 4 ? k_bin_rows_scatter<4, 8, RA> : items == 8 ? k_bin_rows_scatter<8, 8, RA>
                                                                                      : k_bin_rows_scatter<16, 8, RA>);
-    };
-    auto scatter = rank_atomic ? pick(std::true_type{}) : pick(std::false_type{});
+    });
     hipLaunchKernelGGL(scatter, dim3(groups), dim3(256), 0, s, items0, items1, dstats, pay0, pay1, n, groups, hist,
                        row_items, row_pairs, pair_capacity, tiles_y, rows_buf, spans, base, g, cut, cut_mode, cut_n,
                        cstart);
@@ -4691,7 +4554,7 @@ hipError_t launch_bin_cols(const uint64_t* rows_buf, const uint32_t* row_items, 
                            pair_capacity, tiles_x, cbins, gate);
         hipLaunchKernelGGL(k_bin_cols_scan<CH>, dim3(tiles_y), dim3(256), 0, s, row_items, row_pairs, pair_capacity,
                            tiles_x, cbins, ranges, stats, host_mapped_stats, dstats, passes_launched, gate, fstatus);
-        auto pick = [&](auto ra) {
+        auto scatter = with_bool(rank_atomic, [&](auto ra) {
             constexpr bool RA = decltype(ra)::value;
             return tiles_x <= 128
                        ? (items == 4   ? k_bin_cols_scatter<4, 7, RA, CH>
@@ -4700,8 +4563,7 @@ hipError_t launch_bin_cols(const uint64_t* rows_buf, const uint32_t* row_items, 
                        : (items == 4   ? k_bin_cols_scatter<4, 8, RA, CH>
                           : items == 8 ? k_bin_cols_scatter<8, 8, RA, CH>
                                        : k_bin_cols_scatter<16, 8, RA, CH>);
-        };
-        auto scatter = rank_atomic ? pick(std::true_type{}) : pick(std::false_type{});
+        });
         hipLaunchKernelGGL(scatter, dim3(col_groups), dim3(256), 0, s, rows_buf, row_items, row_pairs, pair_capacity,
                            tiles_x, cbins, ranges, vals, gate);
     };

@@ -522,12 +522,7 @@ int bkt_count(int64_t n) {
 constexpr int64_t kBucketSortMaxN = (int64_t)2048 * 1024;
 bool bkt_applies(const gsr_context* c, int64_t n) { return n > 0 && c->bucket_sort != 0; }
 bool bkt_big(const gsr_context* c, int64_t n) { return c->bucket_sort != 3 && n > kBucketSortMaxN; }
-// A/B: GSR_BIG_BUCKETS=1024 sorts 1,024 big buckets with 512-thread workgroups
-int big_bucket_count() {
-    static const int b = [] { const char* e = std::getenv("GSR_BIG_BUCKETS"); return e && std::atoi(e) == 1024 ? 1024 : gsr::kBigBuckets; }();
-    return b;
-}
-int bkt_count(const gsr_context* c, int64_t n) { return bkt_big(c, n) ? big_bucket_count() : bkt_count(n); }
+int bkt_count(const gsr_context* c, int64_t n) { return bkt_big(c, n) ? gsr::kBigBuckets : bkt_count(n); }
 
 // Row items per column-pass chunk (GSR_TUNE_COL_CHUNK 0): 1,024 up to the same 2M
 // Gaussians (config 2: column scatter 26.0 -> 21.6 us, chain -2 us), 2,048 above (config 3:
@@ -1070,8 +1065,7 @@ static int depth_sort_locked(gsr_context* c, bool with_rects, bool plain = false
         if (bkt_big(c, c->n)) {
             // 512 buckets of ~n / 512 items, four 2,048-item tiles per scatter workgroup; the row
             // pass counts for itself (its 2,048-source chunks are cheaper than bucket chunks)
-            static const int g_env = [] { const char* e = std::getenv("GSR_BB_GROUPS"); return e ? std::atoi(e) : 0; }();
-            const int G = std::min(g_env > 0 ? g_env : groups_for(c->n, 4 * gsr::kMaxBucketCap), gsr::kBigBucketGroups);
+            const int G = std::min(groups_for(c->n, 4 * gsr::kMaxBucketCap), gsr::kBigBucketGroups);
             uint32_t* s_in = c->bkt_split + (size_t)c->bkt_par * gsr::kMaxBuckets;
             uint32_t* s_out = c->bkt_split + (size_t)(c->bkt_par ^ 1) * gsr::kMaxBuckets;
             HIP_TRY(gsr::launch_bucket_sort_big(c->pre_out, c->items[0], c->items[1], n, B, G, s_in, s_out, c->hist,
@@ -1237,12 +1231,7 @@ static int bin_locked(gsr_context* c, uint32_t base, uint32_t count, int gate_mo
     // 4,096): 1,024, and 3,072 for a whole-order pass above 2M Gaussians (config 3 orbit, big
     // buckets: the row pass 72.8 -> 65.8 us, the count and scan pay per chunk and the scatter
     // takes 3,072 sources as well as ~1,200; 4,096: 68.7, profiles/r06o_kt_row_chunk_c3.txt).
-    // GSR_ROW_CHUNK forces one size (A/B).
-    static const int64_t row_chunk_env = [] {
-        const char* e = std::getenv("GSR_ROW_CHUNK");
-        return e ? std::max<int64_t>(1024, std::atoll(e)) : (int64_t)0;
-    }();
-    const int64_t row_chunk = row_chunk_env ? row_chunk_env : (!rs && est > kBucketSortMaxN ? 3072 : 1024);
+    const int64_t row_chunk = !rs && est > kBucketSortMaxN ? 3072 : 1024;
     const int gb = std::min(groups_for(est, row_chunk), gsr::kMaxSortGroups / 2);
     // (a bucket-sorted frame has no pass plan: its order is in items[0], its rects in pay_buf 0)
     uint32_t* dst = c->depth_skip && !(c->last_bds && !far) ? (far ? c->dstats_far : c->dstats) : nullptr;

@@ -29,9 +29,9 @@ def torch(gpu):
     return t
 
 
-# big buckets above 2M: 512 (default) or 1,024 (A/B env GSR_BIG_BUCKETS=1024), and their capacity
-BIG = 1024 if os.environ.get("GSR_BIG_BUCKETS") == "1024" else 512
-BIG_CAP = 16384 * 512 // BIG
+# big buckets above 2M, and their capacity
+BIG = 512
+BIG_CAP = 16384
 
 
 def render_frames(gpu, torch, r, scene, cams, W, H):
@@ -54,14 +54,17 @@ def renderer(gpu, buckets=1):
     return r
 
 
-def check_bucket_frame(gpu, orc, torch, scene, soa, cams, W, H, buckets=1, want_over=None, want_work=None):
+def check_bucket_frame(gpu, orc, torch, scene, soa, cams, W, H, buckets=1, want_over=None, want_work=None,
+                       want_buckets=None):
     """Frames over cams on a bucket-sort renderer and on an LSD-only one; the last frame
-    must be bucket-sorted on the first and equal the oracle (order, image) and the LSD
-    renderer (order, tile lists)."""
+    must be bucket-sorted on the first (into want_buckets buckets, when given) and equal the
+    oracle (order, image) and the LSD renderer (order, tile lists)."""
     n = soa.shape[1]
     r = renderer(gpu, buckets)
     img = render_frames(gpu, torch, r, scene, cams, W, H)
     assert r.depth_passes() == 0, "the last frame was not bucket-sorted"
+    if want_buckets is not None:
+        assert r.bucket_sizes().size == want_buckets
     order = r.read_depth_order(n)
     pairs = r.read_pairs()
     over = r.get_tuning(gpu.TUNE_DEPTH_BUCKETS_OVER)
@@ -98,6 +101,18 @@ def test_bucket_sort_config1(gpu, orc, torch, tmp_path_factory):
     W, H = 640, 480
     cams = [cam_for(gpu, W, H)] * 2
     check_bucket_frame(gpu, orc, torch, gpu.Scene.from_soa(soa), soa, cams, W, H, want_over=no_over)
+
+
+@pytest.mark.parametrize("n,buckets", [(300_000, 512), (1_100_000, 2048)])
+def test_bucket_sort_bucket_counts(gpu, orc, torch, tmp_path_factory, n, buckets):
+    """The smallest scenes that select the 512- and 2,048-bucket kernels of the small kind
+    (256: config 1 above; 1,024: config 2 below; 4,096: test_bucket_kind_by_size, knob 3),
+    on general depths: 640x480, two frames on a fixed camera."""
+    _, soa = scene_soa(gpu, tmp_path_factory, n, 22)
+    W, H = 640, 480
+    cams = [cam_for(gpu, W, H)] * 2
+    check_bucket_frame(gpu, orc, torch, gpu.Scene.from_soa(soa), soa, cams, W, H, want_over=no_over,
+                       want_buckets=buckets)
 
 
 def test_bucket_sort_config2_full(gpu, orc, torch, tmp_path_factory):
