@@ -21,7 +21,7 @@ from ctypes import byref, c_float, c_int, c_int64, c_void_p
 import numpy as np
 
 from . import _native
-from ._native import (Camera, GsrError, LAYOUT_AOS, LAYOUT_SCENE_BLOCK, LAYOUT_SCENE_BLOCK_4D,
+from ._native import (AUX_MAX_FEATURES, AuxTargets, Camera, GsrError, LAYOUT_AOS, LAYOUT_SCENE_BLOCK, LAYOUT_SCENE_BLOCK_4D,
                       LAYOUT_SCENE_BLOCK_SH3, NUM_STAGES, PLY_SH3, PLY_TYPED, SCENE4D_NARRAYS, SCENE_NARRAYS,
                       SCENE_SH3_NARRAYS,
                       SPLAT_RECORD_BYTES, STAGES, TILE_PX, check, lib)
@@ -29,7 +29,7 @@ from ._native import (Camera, GsrError, LAYOUT_AOS, LAYOUT_SCENE_BLOCK, LAYOUT_S
 __all__ = [
     "Camera", "GsrError", "Renderer", "Scene", "TilingInformation", "make_camera", "orbit",
     "loadGaussianCudaFromPly", "preprocessCUDAGaussians", "read_ply", "write_synthetic_ply",
-    "SPLAT_DTYPE", "STAGES", "TILE_PX", "lib", "DisplayTarget", "display_gl_current", "preprocessCUDAGaussiansGL",
+    "SPLAT_DTYPE", "STAGES", "TILE_PX", "lib", "AUX_MAX_FEATURES", "DisplayTarget", "display_gl_current", "preprocessCUDAGaussiansGL",
 ]
 
 # gsr_read_splats record (include/gsr.h).
@@ -298,6 +298,39 @@ class Renderer:
                               t.width_stride, t.height_stride, k, out_ptr, stream or None)
         if rc not in (_native.GSR_OK, _native.GSR_E_OVERFLOW):
             raise GsrError(rc, "gsr_render")
+        return rc
+
+    def render_aux(self, scene, cam: Camera, W: int, H: int, out_ptr: int | None = None,
+                   alpha_ptr: int | None = None, depth_ptr: int | None = None, features_ptr: int | None = None,
+                   nfeat: int = 0, feat_out_ptr: int | None = None, k: float = 3.0, tiling=None, stream: int = 0,
+                   layout: int = LAYOUT_SCENE_BLOCK, n: int | None = None, time: float | None = None) -> int:
+        """Enqueue one frame with auxiliary targets (gsr_render_aux, include/gsr.h), each a
+        device buffer or None: out_ptr the image (3*W*H float32, the exact blend's),
+        alpha_ptr the accumulated alpha (W*H), depth_ptr the un-normalised depth sum (W*H;
+        the expected depth is depth / alpha), and feat_out_ptr nfeat*W*H floats composited
+        from features_ptr (nfeat arrays of n floats, feature f of Gaussian i at [f*n + i]).
+        Same returns as render()."""
+        nfeat = int(nfeat)
+        if not 0 <= nfeat <= AUX_MAX_FEATURES:
+            raise ValueError(f"render_aux: nfeat must be 0..{AUX_MAX_FEATURES}")
+        if nfeat and not (features_ptr and feat_out_ptr):
+            raise ValueError("render_aux: nfeat > 0 needs features_ptr and feat_out_ptr")
+        if not nfeat and (features_ptr or feat_out_ptr):
+            raise ValueError("render_aux: features_ptr / feat_out_ptr given with nfeat = 0")
+        if not (out_ptr or alpha_ptr or depth_ptr or nfeat):
+            raise ValueError("render_aux: no output requested")
+        ptr = scene.ptr if isinstance(scene, Scene) else int(scene)
+        n = scene.n if n is None else n
+        if isinstance(scene, Scene) and layout == LAYOUT_SCENE_BLOCK:
+            layout = scene.layout
+        if time is not None:
+            self.set_time(time)
+        t = tiling or TilingInformation(1, 1, H, W)
+        aux = AuxTargets(alpha_ptr or None, depth_ptr or None, features_ptr or None, nfeat, feat_out_ptr or None)
+        rc = lib().gsr_render_aux(self.ctx, ptr, layout, n, byref(cam), W, H, t.num_tile_x, t.num_tile_y,
+                                  t.width_stride, t.height_stride, k, out_ptr or None, byref(aux), stream or None)
+        if rc not in (_native.GSR_OK, _native.GSR_E_OVERFLOW):
+            raise GsrError(rc, "gsr_render_aux")
         return rc
 
     def set_frames_in_flight(self, frames: int):

@@ -86,6 +86,21 @@ class Lwg(ctypes.Structure):
 
 assert ctypes.sizeof(Lwg) == 16
 
+AUX_MAX_FEATURES = 8   # GSR_AUX_MAX_FEATURES
+
+
+class AuxTargets(ctypes.Structure):
+    """``gsr_aux_targets`` (include/gsr.h): the extra outputs of gsr_render_aux."""
+
+    _fields_ = [
+        ("d_alpha", c_void_p),
+        ("d_depth", c_void_p),
+        ("d_features", c_void_p),
+        ("nfeat", c_int),
+        ("d_feat_out", c_void_p),
+    ]
+
+
 # (name, restype, argtypes) for every symbol of include/gsr.h and include/gsr_gl.h.
 SIGNATURES = [
     ("preprocessCUDAGaussians", None,
@@ -108,6 +123,8 @@ SIGNATURES = [
     ("gsr_reserve", c_int, [c_void_p, c_int64, c_int64]),
     ("gsr_render", c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(Camera), c_int, c_int, c_int, c_int,
                            c_int, c_int, c_float, c_void_p, c_void_p]),
+    ("gsr_render_aux", c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(Camera), c_int, c_int, c_int, c_int,
+                               c_int, c_int, c_float, c_void_p, POINTER(AuxTargets), c_void_p]),
     ("gsr_render_path", c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(Camera), c_void_p, c_int, c_int,
                                 c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     ("gsr_render_path_ex", c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(Camera), c_void_p, c_int, c_int,

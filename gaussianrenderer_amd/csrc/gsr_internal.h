@@ -204,6 +204,19 @@ hipError_t launch_kv_pass(const void* keys_in, const uint32_t* vals_in, void* ke
 hipError_t launch_blend(const uint32_t* idx, const uint2* ranges, const uint4* rec, const Frame& fr,
                         float* out, unsigned long long* consumed, bool stamps, int band_tiles, int blend_exp,
                         hipStream_t s, const BlendSplit* split = nullptr);
+// Auxiliary render targets (gsr_render_aux).  launch_aux_depth: z[i] = -Z of Gaussian i, the
+// view-space z behind its depth key (n floats; arrays / stride / four_d / t as given to
+// launch_preprocess).  launch_blend_aux (k_blend_aux): the exact blend over the same lists
+// with k_blend_w's schedule, writing the colour planes (out, nullable), the accumulated
+// alpha and the un-normalised depth (one plane each, nullable; depth needs z) and nfeat
+// <= 8 feature planes (feat_out) composited from features (nfeat arrays of n floats); pack:
+// 2 n float4 of workspace for nfeat > 4 (the features interleaved per Gaussian, k_aux_pack).
+hipError_t launch_aux_depth(const float* arrays, int64_t stride, int64_t n, const Frame& fr, bool four_d, float t,
+                            float* z, hipStream_t s);
+hipError_t launch_blend_aux(const uint32_t* idx, const uint2* ranges, const uint4* rec, const Frame& fr,
+                            float* out, float* alpha, float* depth, const float* z, const float* features,
+                            int64_t n, int nfeat, float* feat_out, float4* pack, int band_tiles,
+                            hipStream_t s);
 // Stable partition of the preprocess items: visible first, culled last (both in
 // index order), visible count into *n_live; culled tail to out only, with dead
 // rects in srect (gsr_kernels.hip "live partition").  counts: groups words.

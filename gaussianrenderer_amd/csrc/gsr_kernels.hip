@@ -4124,6 +4124,278 @@ __global__ __launch_bounds__(64, 8) void k_blend_w(const uint32_t* __restrict__ 
     }
 }
 
+// ------------------------------------------------------------------ auxiliary render targets
+
+// -Z of every Gaussian (gsr_render_aux's depth channel): Z is the view-space z of
+// preprocess_one — the same position (4D: at tnow, the same expression) through the same
+// mv4 — so -Z is the float whose scaled value becomes the depth key, the positive distance
+// along the view axis.  Culled Gaussians get whatever the product gives; no list holds them.
+template <bool T4D>
+__global__ __launch_bounds__(256) void k_aux_depth(const float* __restrict__ arr, int64_t stride, int64_t n,
+                                                   Frame fr, float tnow, float* __restrict__ z) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    auto A = [&](int64_t k) { return arr[k * stride + i]; };
+    float gx = A(GSR_A_X);
+    float gy = A(GSR_A_Y);
+    float gz = A(GSR_A_Z);
+    if (T4D) {
+        const float dt = tnow - A(GSR_A_TCENTER);
+        const float dt2 = dt * dt, dt3 = dt2 * dt;
+        auto m = [&](int j) { return A(GSR_A_MOTION0 + j); };
+        gx = ((gx + m(0) * dt) + m(3) * dt2) + m(6) * dt3;
+        gy = ((gy + m(1) * dt) + m(4) * dt2) + m(7) * dt3;
+        gz = ((gz + m(2) * dt) + m(5) * dt2) + m(8) * dt3;
+    }
+    const float old_xyz[4] = {gx, gy, gz, 1.0f};
+    float tmp_xyz[4];
+    mv4(fr.V, old_xyz, tmp_xyz);
+    z[i] = -tmp_xyz[2];
+}
+
+// The 8-channel kernel's feature values interleaved per Gaussian: pack[2 i] and pack[2 i + 1]
+// hold features 0-3 and 4-7 of Gaussian i (0 from nfeat on).  The arrays are planar and the
+// blend gathers by scattered Gaussian index, so each planar value costs a survivor a cache
+// line of its own; interleaved, its eight values are one 32-B piece of one line.  Coalesced
+// both ways (4 nfeat + 32 bytes per Gaussian).
+__global__ __launch_bounds__(256) void k_aux_pack(const float* __restrict__ features, int64_t n, int nfeat,
+                                                  float4* __restrict__ pack) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float v[8];
+#pragma unroll
+    for (int f = 0; f < 8; f++) v[f] = f < nfeat ? features[(int64_t)f * n + i] : 0.0f;
+    pack[2 * i] = make_float4(v[0], v[1], v[2], v[3]);
+    pack[2 * i + 1] = make_float4(v[4], v[5], v[6], v[7]);
+}
+
+// Where k_blend_aux reads its per-Gaussian values and writes its planes (nullable each;
+// feat / features with nfeat > 0).
+struct AuxIO {
+    float* color;            // 3 planes
+    float* alpha;
+    float* depth;
+    float* feat;             // nfeat planes
+    const float* features;   // nfeat arrays of n floats (NF = 4)
+    const float4* pack;      // k_aux_pack's output (NF = 8)
+    const float* z;          // k_aux_depth's output (depth != nullptr)
+    int64_t n;
+    int nfeat;
+};
+
+// The blend with auxiliary targets (gsr_render_aux): k_blend_w's schedule — one wave64 per
+// 8x8 block, one-wave workgroups, the same block -> workgroup mapping and tile lists, the
+// same 64-record batches, prefetch and conservative cull — and, for every survivor, the
+// exact one-splat step of blend_block (gsr_blend_md2, gsr_blend_expf, selects), so each
+// pixel takes the decisions of render.cu:323-341 and the colours are the exact blend's
+// bit for bit.  Every other channel accumulates like a colour, acc = fma(v alpha, T, acc)
+// in list order: v = 1 (alpha: the accumulated coverage), v = -Z (depth, un-normalised)
+// and v = the Gaussian's feature values.  Only a surviving lane gathers its splat's -Z
+// and features (by Gaussian index; the records do not hold them): up to four from the
+// planar arrays, more from k_aux_pack's interleaved copy.
+//
+// Survivor k's slot in the wave's LDS slice (12 + NF dwords, 16-B aligned, read with
+// wave-uniform addresses):
+//   [0] cx [1] cy [2] a [3] b | [4] c [5] e [6] opacity [7] red | [8] green [9] blue
+//   [10] -Z [11] unused | [12 ..] features
+// NF = 0 / 4 / 8: 3 / 4 / 5 KiB per wave.  Eight waves per SIMD of NF = 8 would need the
+// CU's whole 160 KiB and squeeze its 13 accumulators into 64 VGPRs, so that instantiation
+// asks for six or more (with colour it compiles to 69 VGPRs: seven waves, 140 KiB, no spill); the
+// others keep k_blend_w's eight.
+// COLOR false: no colour planes (the colour accumulations drop out).
+template <int NF, bool COLOR>
+__global__ __launch_bounds__(64, NF > 4 ? 6 : 8) void k_blend_aux(const uint32_t* __restrict__ idx,
+                                                                 const uint2* __restrict__ ranges,
+                                                                 const uint4* __restrict__ rec, int tiles_x,
+                                                                 int tiles_y, int W, int H, int cover_w,
+                                                                 int cover_h, int bands, AuxIO io) {
+    constexpr int kSlot = 12 + NF;                          // dwords per survivor slot
+    constexpr int kNF = NF ? NF : 1;
+    __shared__ float4 sP[64 * kSlot / 4];
+    const int ntiles = tiles_x * tiles_y;
+    const int vb = (int)blockIdx.x;
+    int L;
+    if (bands > 1) {
+        const int nu = 4 * ntiles;
+        const int B = (nu + 8 * bands - 1) / (8 * bands);
+        const int k = vb >> 3;
+        L = ((k / B) * 8 + (vb & 7)) * B + k % B;
+        if (L >= nu) return;
+    } else {
+        if (vb >= ntiles * 4) return;
+        L = xcd_remap(vb, ntiles * 4);
+    }
+    const int tile = L >> 2, sub = L & 3;
+    const int tx = tile % tiles_x, ty = tile / tiles_x;
+    const int lane = (int)(threadIdx.x & 63u);
+    const uint2 rr = ranges[tile];                          // {~start, end}, zero = empty
+    const uint32_t beg = rr.y ? ~rr.x : 0u, end = rr.y;
+    const int bx = tx * GSR_TILE_PX + (sub & 1) * 8, by = ty * GSR_TILE_PX + (sub >> 1) * 8;
+    const float4* wP4 = sP;
+
+    const int px = bx + (lane & 7), py = by + (lane >> 3);
+    const bool inside = px < cover_w && py < cover_h;
+    const float fpx = (float)px, fpy = (float)py;
+    // pixels outside the covered area start saturated and write 0 (blend_block)
+    float T = inside ? 1.0f : 0.0f;
+    float cr = 0.0f, cg = 0.0f, cb = 0.0f, ca = 0.0f, cz = 0.0f, cf[kNF];
+#pragma unroll
+    for (int f = 0; f < kNF; f++) cf[f] = 0.0f;
+
+    uint4 ra = make_uint4(0, 0, 0, 0), rb = ra, rc = ra, rd = ra;
+    uint32_t nidx = 0, cidx = 0;
+    if (beg + lane < end) {
+        cidx = idx[beg + lane];
+        const uint4* R = rec + 4 * (uint64_t)cidx;
+        ra = R[0];
+        rb = R[1];
+        rc = R[2];
+        rd = R[3];
+    }
+    if (beg + 64 + lane < end) nidx = idx[beg + 64 + lane];
+    bool alive = __ballot(!(T < 1e-3f)) != 0ull;
+    for (uint32_t base = beg; base < end && alive; base += 64) {
+        const uint32_t cnt = min(64u, end - base);
+        // ---- cull (lane = record): blend_block's, AABB vs block, the live-pixel filter,
+        // then the ellipse-vs-block test ----
+        const uint64_t live_b = __ballot(!(T < 1e-3f));
+        bool hit;
+        uint32_t dsc;
+        {
+            const bool valid = (uint32_t)lane < cnt;
+            const int xmin = (int)(rc.z & 0xffffu), xmax = (int)(rc.z >> 16);
+            const int ymin = (int)(rc.w & 0xffffu), ymax = (int)(rc.w >> 16);
+            const bool box_hit = valid & !((xmax < bx) | (xmin > bx + 7) | (ymax < by) | (ymin > by + 7));
+            const float cx = __uint_as_float(rc.x), cy = __uint_as_float(rc.y);
+            const float a = __uint_as_float(ra.x), b = __uint_as_float(ra.y);
+            const float c = __uint_as_float(ra.z), e = __uint_as_float(ra.w);
+            const int x0 = max(xmin - bx, 0), x1 = min(xmax - bx, 7);
+            const int y0 = max(ymin - by, 0), y1 = min(ymax - by, 7);
+            const float dx0 = (float)(bx + x0) - cx, dx1 = (float)(bx + x1) - cx;
+            const float dy0 = (float)(by + y0) - cy, dy1 = (float)(by + y1) - cy;
+            // box descriptor (box_mask); shift counts masked to the hardware's: only lanes
+            // outside the box can have them out of range, and their results are discarded
+            const uint32_t colb = (0xffu >> ((uint32_t)(7 - (x1 - x0)) & 31u)) << ((uint32_t)x0 & 31u);
+            const uint32_t rsh = (uint32_t)(56 - 8 * (y1 - y0)) & 63u, lsh = (uint32_t)(8 * y0) & 63u;
+            dsc = colb | (rsh << 8) | (lsh << 16);
+            const uint64_t rows = (~0ull >> rsh) << lsh;
+            const uint32_t rep = __builtin_amdgcn_perm(colb, colb, 0u);   // colb in every byte
+            const uint64_t lrows = rows & live_b;
+            const float S = __uint_as_float(rd.w);
+            const float M = fmaxf(fmaxf(fabsf(dx0), fabsf(dx1)), fmaxf(fabsf(dy0), fabsf(dy1)));
+            const float SMM = S * M * M;
+            hit = box_hit & ((((uint32_t)lrows | (uint32_t)(lrows >> 32)) & rep) != 0u) &
+                  block_may_reach(a, b, c, e, __uint_as_float(rd.y), __uint_as_float(rd.z), dx0, dx1, dy0, dy1,
+                                  SMM, block_cut(__uint_as_float(rd.x)));
+        }
+        // ---- survivors, compacted in list order; each gathers its -Z and features ----
+        const uint64_t m = __ballot(hit);
+        const uint32_t k_l = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        float zv = 0.0f, fv[kNF];
+#pragma unroll
+        for (int f = 0; f < kNF; f++) fv[f] = 0.0f;
+        if (hit) {
+            if (io.z) zv = io.z[cidx];
+            if (NF == 8) {
+                const float4 p0 = io.pack[2 * (int64_t)cidx], p1 = io.pack[2 * (int64_t)cidx + 1];
+                fv[0] = p0.x; fv[1 % kNF] = p0.y; fv[2 % kNF] = p0.z; fv[3 % kNF] = p0.w;
+                fv[4 % kNF] = p1.x; fv[5 % kNF] = p1.y; fv[6 % kNF] = p1.z; fv[7 % kNF] = p1.w;
+            } else {
+#pragma unroll
+                for (int f = 0; f < NF; f++)   // padding channels repeat the last array (never stored)
+                    fv[f] = io.features[(int64_t)min(f, io.nfeat - 1) * io.n + (int64_t)cidx];
+            }
+            float4* S4 = sP + k_l * (kSlot / 4);
+            S4[0] = make_float4(__uint_as_float(rc.x), __uint_as_float(rc.y), __uint_as_float(ra.x),
+                                __uint_as_float(ra.y));
+            S4[1] = make_float4(__uint_as_float(ra.z), __uint_as_float(ra.w), __uint_as_float(rb.x),
+                                __uint_as_float(rb.y));
+        }
+        const float col_g = __uint_as_float(rb.z), col_b = __uint_as_float(rb.w);
+        // ---- prefetch: records of batch k+1, indices of batch k+2 ----
+        if (base + 64 + lane < end) {
+            cidx = nidx;
+            const uint4* R = rec + 4 * (uint64_t)nidx;
+            ra = R[0];
+            rb = R[1];
+            rc = R[2];
+            rd = R[3];
+        }
+        if (base + 128 + lane < end) nidx = idx[base + 128 + lane];
+        if (hit) {
+            // (the gathered values last: their loads were issued ahead of the prefetch)
+            float4* S4 = sP + k_l * (kSlot / 4);
+            S4[2] = make_float4(col_g, col_b, zv, 0.0f);
+            if (NF >= 4) S4[3] = make_float4(fv[0], fv[1 % kNF], fv[2 % kNF], fv[3 % kNF]);
+            if (NF >= 8) S4[4] = make_float4(fv[4 % kNF], fv[5 % kNF], fv[6 % kNF], fv[7 % kNF]);
+        }
+        // ---- the exact one-splat step over the survivors (render.cu:329-340) ----
+        uint64_t mm = m;
+        for (uint32_t k = 0; mm && alive; ++k) {
+            const int s = __builtin_ctzll(mm);
+            mm &= mm - 1;
+            const uint64_t box = box_mask((uint32_t)__builtin_amdgcn_readlane((int)dsc, s));
+            const float4 q0 = wP4[k * (kSlot / 4) + 0], q1 = wP4[k * (kSlot / 4) + 1];
+            const float4 q2 = wP4[k * (kSlot / 4) + 2];
+            const float dx = fpx - q0.x, dy = fpy - q0.y;
+            const float md = gsr_blend_md2(dx, dy, q0.z, q0.w, q1.x, q1.y);
+            const float ee = gsr_blend_expf(-0.5f * md);
+            float alpha = q1.z * ee;
+            alpha = fminf(alpha, 0.99f);
+            const bool in = __builtin_amdgcn_inverse_ballot_w64(box);
+            const bool take = in & !(T < 1e-3f) & !(alpha < 1e-3f);
+            if (COLOR) {
+                const float wr = __builtin_fmaf(q1.w * alpha, T, cr);
+                const float wg = __builtin_fmaf(q2.x * alpha, T, cg);
+                const float wb = __builtin_fmaf(q2.y * alpha, T, cb);
+                cr = take ? wr : cr;
+                cg = take ? wg : cg;
+                cb = take ? wb : cb;
+            }
+            // alpha's value is 1.0f: 1.0f * alpha is alpha exactly
+            const float wa = __builtin_fmaf(alpha, T, ca);
+            const float wz = __builtin_fmaf(q2.z * alpha, T, cz);
+            ca = take ? wa : ca;
+            cz = take ? wz : cz;
+            if (NF >= 4) {
+                const float4 q3 = wP4[k * (kSlot / 4) + 3];
+                const float v[4] = {q3.x, q3.y, q3.z, q3.w};
+#pragma unroll
+                for (int f = 0; f < 4; f++) {
+                    const float wf = __builtin_fmaf(v[f] * alpha, T, cf[f % kNF]);
+                    cf[f % kNF] = take ? wf : cf[f % kNF];
+                }
+            }
+            if (NF >= 8) {
+                const float4 q4 = wP4[k * (kSlot / 4) + 4];
+                const float v[4] = {q4.x, q4.y, q4.z, q4.w};
+#pragma unroll
+                for (int f = 0; f < 4; f++) {
+                    const float wf = __builtin_fmaf(v[f] * alpha, T, cf[(4 + f) % kNF]);
+                    cf[(4 + f) % kNF] = take ? wf : cf[(4 + f) % kNF];
+                }
+            }
+            const float Tn = T * (1.0f - alpha);
+            T = take ? Tn : T;
+            alive = __ballot(!(T < 1e-3f)) != 0ull;
+        }
+    }
+    if (px < W && py < H) {
+        const size_t o = (size_t)py * (size_t)W + (size_t)px;
+        const size_t hw = (size_t)W * (size_t)H;
+        if (COLOR) {
+            io.color[o] = inside ? cr : 0.0f;
+            io.color[hw + o] = inside ? cg : 0.0f;
+            io.color[2 * hw + o] = inside ? cb : 0.0f;
+        }
+        if (io.alpha) io.alpha[o] = inside ? ca : 0.0f;
+        if (io.depth) io.depth[o] = inside ? cz : 0.0f;
+#pragma unroll
+        for (int f = 0; f < NF; f++)
+            if (f < io.nfeat) io.feat[(size_t)f * hw + o] = inside ? cf[f] : 0.0f;
+    }
+}
+
 // ------------------------------------------------------------------ standalone sort ABI helpers
 
 // (u32(key) << 32 | i): the reference sorts int keys as unsigned 8-bit digits
@@ -4657,6 +4929,48 @@ hipError_t launch_blend(const uint32_t* idx, const uint2* ranges, const uint4* r
     }
 #undef GSR_BLEND
 #undef GSR_BLEND_S
+    return hipGetLastError();
+}
+
+hipError_t launch_aux_depth(const float* arrays, int64_t stride, int64_t n, const Frame& fr, bool four_d, float t,
+                            float* z, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    const dim3 g(grid_for(n, 256));
+    if (four_d) hipLaunchKernelGGL((k_aux_depth<true>), g, dim3(256), 0, s, arrays, stride, n, fr, t, z);
+    else hipLaunchKernelGGL((k_aux_depth<false>), g, dim3(256), 0, s, arrays, stride, n, fr, t, z);
+    return hipGetLastError();
+}
+
+hipError_t launch_blend_aux(const uint32_t* idx, const uint2* ranges, const uint4* rec, const Frame& fr,
+                            float* out, float* alpha, float* depth, const float* z, const float* features,
+                            int64_t n, int nfeat, float* feat_out, float4* pack, int band_tiles,
+                            hipStream_t s) {
+    if (nfeat < 0 || nfeat > 8 || (nfeat > 0 && (!features || !feat_out)) || (depth && n > 0 && !z) ||
+        (nfeat > 4 && n > 0 && !pack) ||
+        (!out && !alpha && !depth && nfeat == 0))
+        return hipErrorInvalidValue;
+    const int nt = fr.tiles_x * fr.tiles_y;
+    if (nt <= 0) return hipSuccess;
+    // the grid of launch_blend: bands of band_tiles tiles dealt round-robin to the 8 XCDs
+    int bands = 1, ng = 4 * nt;
+    if (band_tiles > 0 && (nt + 8 * band_tiles - 1) / (8 * band_tiles) > 1) {
+        bands = (nt + 8 * band_tiles - 1) / (8 * band_tiles);
+        ng = 8 * bands * ((4 * nt + 8 * bands - 1) / (8 * bands));
+    }
+    if (nfeat > 4 && n > 0)
+        hipLaunchKernelGGL(k_aux_pack, dim3(grid_for(n, 256)), dim3(256), 0, s, features, n, nfeat, pack);
+    const AuxIO io{out, alpha, depth, feat_out, features, pack, depth ? z : nullptr, n, nfeat};
+    // features padded to 0 / 4 / 8 channels
+    auto go = [&](auto nf) {
+        constexpr int NF = decltype(nf)::value;
+        with_bool(out != nullptr, [&](auto color) {
+            hipLaunchKernelGGL((k_blend_aux<NF, decltype(color)::value>), dim3(ng), dim3(64), 0, s, idx, ranges, rec,
+                               fr.tiles_x, fr.tiles_y, fr.W, fr.H, fr.cover_w, fr.cover_h, bands, io);
+        });
+    };
+    if (nfeat == 0) go(std::integral_constant<int, 0>{});
+    else if (nfeat <= 4) go(std::integral_constant<int, 4>{});
+    else go(std::integral_constant<int, 8>{});
     return hipGetLastError();
 }
 

@@ -452,6 +452,12 @@ struct gsr_context {
     bool last_bds = false;           // the last sorted frame was bucket-sorted (order in items[0], no pass plan)
     bool bkt_rows_fused = false;     // its local sorts wrote the row pass's counts (bucket = row chunk): the
                                      // next binning skips its count kernel (once: the row scan consumes them)
+    int split_state_hold = -1;       // >= 0: the sorted frame is an aux frame (gsr_render_aux), and
+                                     // GSR_TUNE_DEPTH_SPLIT_STATE reads this, the state of the frame before it
+    float* aux_z = nullptr;          // gsr_render_aux: -Z per Gaussian (the depth channel's values)
+    int64_t aux_z_cap = 0;
+    float4* aux_pack = nullptr;      // gsr_render_aux, nfeat > 4: the features interleaved per Gaussian
+    int64_t aux_pack_cap = 0;
     int fail_frame = 0;              // GSR_TUNE_FAIL_FRAME: gsr_render_path fails this frame (> 0) once
     uint32_t* fstatus = nullptr;     // the current frame's validity word (gsr_render_path_status; device,
                                      // nullable): GSR_FRAME_* bits, written by its column scans / blend
@@ -704,6 +710,12 @@ void mark(gsr_context* c, int stage) {
     (void)hipEventRecord(e, c->stream);
 }
 
+// GSR_TUNE_DEPTH_SPLIT_STATE: how the last sorted frame ran (aux frames do not count).
+int split_state(const gsr_context* c) {
+    if (c->split_state_hold >= 0) return c->split_state_hold;
+    return !c->split_frame ? 0 : !c->frame_key ? 1 : c->frame_spec ? 3 : 2;
+}
+
 // The split point and the controller's epoch as phase B publishes them (Stats::split_pm).
 uint32_t split_tag(const gsr_context* c) { return (uint32_t)c->split_pm | ((c->split_epoch & 0xffffu) << 16); }
 
@@ -886,7 +898,7 @@ extern "C" void gsr_destroy(gsr_context* c) {
                     (void*)c->ranges, (void*)c->soa_tmp, (void*)c->out_tmp, (void*)c->consumed, (void*)c->binmeta,
                     (void*)c->cbins, (void*)c->srect, (void*)c->spans, (void*)c->nlive, (void*)c->tbuf,
                     (void*)c->bflag, (void*)c->gate, (void*)c->kcut, (void*)c->dstats_far, (void*)c->kcut_frame,
-                    (void*)c->src_items, (void*)c->sat, (void*)c->nfar, (void*)c->bkt_rec})
+                    (void*)c->src_items, (void*)c->sat, (void*)c->nfar, (void*)c->bkt_rec, (void*)c->aux_z, (void*)c->aux_pack})
         if (p) (void)hipFree(p);
     if (c->hstats) (void)hipHostFree(c->hstats);
     if (c->done_ev) (void)hipEventDestroy(c->done_ev);
@@ -1266,6 +1278,7 @@ static int sort_locked(gsr_context* c, bool allow_split) {
     const uint32_t n = (uint32_t)c->n;
     const bool bin = c->rect_packed;   // the path gsr_preprocess chose (its rect format)
     c->last_binned = bin;
+    c->split_state_hold = -1;
     // depth split for this frame (gsr_render / gsr_render_path on the binning path):
     // count mode sorts the whole order and phase A bins its nearest na positions; key
     // mode (a threshold from an earlier split frame exists) partitions by the threshold
@@ -1467,6 +1480,142 @@ extern "C" int gsr_render(gsr_context* c, const void* scene, int layout, int64_t
     if (int r2 = sort_locked(c, true)) return r2;
     if (int r3 = blend_locked(c, d_out)) return r3;
     return rc;
+}
+
+// ------------------------------------------------------------------ auxiliary render targets
+
+namespace {
+
+// The depth split's controller: what check_overflow and the preprocess adapt from frame to
+// frame.  An aux frame takes no part in it (gsr_render_aux saves and restores it).
+struct SplitCtl {
+    int split_pm, split_floor, split_clean, split_off_frames, split_retry;
+    uint32_t split_epoch;
+    bool split_seen, split_spec, split_key_ready;
+    float split_off_view[32], prev_view[32], split_view[32];
+};
+
+void split_ctl_save(const gsr_context* c, SplitCtl* s) {
+    s->split_pm = c->split_pm;
+    s->split_floor = c->split_floor;
+    s->split_clean = c->split_clean;
+    s->split_off_frames = c->split_off_frames;
+    s->split_retry = c->split_retry;
+    s->split_epoch = c->split_epoch;
+    s->split_seen = c->split_seen;
+    s->split_spec = c->split_spec;
+    s->split_key_ready = c->split_key_ready;
+    std::memcpy(s->split_off_view, c->split_off_view, sizeof s->split_off_view);
+    std::memcpy(s->prev_view, c->prev_view, sizeof s->prev_view);
+    std::memcpy(s->split_view, c->split_view, sizeof s->split_view);
+}
+
+void split_ctl_restore(gsr_context* c, const SplitCtl& s) {
+    c->split_pm = s.split_pm;
+    c->split_floor = s.split_floor;
+    c->split_clean = s.split_clean;
+    c->split_off_frames = s.split_off_frames;
+    c->split_retry = s.split_retry;
+    c->split_epoch = s.split_epoch;
+    c->split_seen = s.split_seen;
+    c->split_spec = s.split_spec;
+    c->split_key_ready = s.split_key_ready;
+    std::memcpy(c->split_off_view, s.split_off_view, sizeof s.split_off_view);
+    std::memcpy(c->prev_view, s.prev_view, sizeof s.prev_view);
+    std::memcpy(c->split_view, s.split_view, sizeof s.split_view);
+}
+
+// The aux frame's -Z array (n floats), grown like the other per-Gaussian buffers.
+int ensure_aux_z(gsr_context* c, int64_t n) {
+    if (n <= c->aux_z_cap) return GSR_OK;
+    const int64_t cap = std::max<int64_t>(n, 1024);
+    HIP_TRY(hipDeviceSynchronize());
+    if (int rc = realloc_dev(&c->aux_z, (size_t)cap)) return rc;
+    c->aux_z_cap = cap;
+    return GSR_OK;
+}
+
+// More than four features: their interleaved copy (2 float4 per Gaussian).
+int ensure_aux_pack(gsr_context* c, int64_t n) {
+    if (n <= c->aux_pack_cap) return GSR_OK;
+    const int64_t cap = std::max<int64_t>(n, 1024);
+    HIP_TRY(hipDeviceSynchronize());
+    if (int rc = realloc_dev(&c->aux_pack, 2 * (size_t)cap)) return rc;
+    c->aux_pack_cap = cap;
+    return GSR_OK;
+}
+
+// The sorted frame's blend with auxiliary targets: blend_locked's one-phase frame with
+// k_blend_aux in place of k_blend_w, and no diagnostics.
+int blend_aux_locked(gsr_context* c, float* d_out, const gsr_aux_targets& aux) {
+    const bool with_z = aux.d_depth && c->n > 0;
+    if (with_z) {
+        if (int rc = ensure_aux_z(c, c->n)) return rc;
+    }
+    if (aux.nfeat > 4 && c->n > 0) {
+        if (int rc = ensure_aux_pack(c, c->n)) return rc;
+    }
+    mark(c, GSR_STAGE_BLEND);   // the stage holds the -Z and feature-pack kernels too
+    if (with_z)
+        HIP_TRY(gsr::launch_aux_depth(c->pre_arrays, c->pre_stride, c->n, c->fr,
+                                      c->pre_layout == GSR_LAYOUT_SCENE_BLOCK_4D, c->time, c->aux_z, c->stream));
+    HIP_TRY(gsr::launch_blend_aux(pair_vals(c, c->pair_buf), c->ranges, c->rec, c->fr, d_out, aux.d_alpha,
+                                  aux.d_depth, c->aux_z, aux.d_features, c->n, aux.nfeat, aux.d_feat_out, c->aux_pack,
+                                  c->blend_band_tiles, c->stream));
+    mark(c, GSR_NUM_STAGES);
+    if (c->timing && c->timing_now) c->ev_frames.push_back(c->cur);
+    c->cur = FrameEvents{};
+    if (!c->pending && c->completion_events) {
+        HIP_TRY(hipEventRecord(c->done_ev, c->stream));
+        c->pending = true;
+    }
+    return GSR_OK;
+}
+
+}  // namespace
+
+extern "C" int gsr_render_aux(gsr_context* c, const void* scene, int layout, int64_t n, const gsr_camera* cam,
+                              int W, int H, int nx, int ny, int ws, int hs, float k, float* d_out,
+                              const gsr_aux_targets* aux, void* stream) {
+    if (!c) return set_err(GSR_E_ARG, "null context");
+    if (!aux) return set_err(GSR_E_ARG, "gsr_render_aux: null aux targets");
+    if (aux->nfeat < 0 || aux->nfeat > GSR_AUX_MAX_FEATURES)
+        return set_err(GSR_E_ARG, "gsr_render_aux: nfeat %d out of range [0, %d]", aux->nfeat, GSR_AUX_MAX_FEATURES);
+    if (aux->nfeat > 0 && (!aux->d_features || !aux->d_feat_out))
+        return set_err(GSR_E_ARG, "gsr_render_aux: nfeat %d needs d_features and d_feat_out", aux->nfeat);
+    if (!d_out && !aux->d_alpha && !aux->d_depth && aux->nfeat == 0)
+        return set_err(GSR_E_ARG, "gsr_render_aux: no output");
+    std::lock_guard<std::mutex> lk(c->mu);
+    // One phase, exact blend, and the depth split's controller untouched: the preprocess
+    // and the sort run with the split off (no threshold partition, no partial records, no
+    // retry bookkeeping), and what the preprocess's overflow check learned from earlier
+    // split frames is put back for the next non-aux frame's check to learn again (their
+    // evidence is sticky) — unless that check reported an incomplete frame, whose
+    // consequences (no more speculation) stand.
+    SplitCtl ctl;
+    split_ctl_save(c, &ctl);
+    const int state = split_state(c);
+    const int depth_split = c->depth_split;
+    c->depth_split = 0;
+    int rc = preprocess_locked(c, scene, layout, n, cam, W, H, nx, ny, ws, hs, k, stream);
+    int r2 = GSR_OK;
+    if (rc == GSR_OK || rc == GSR_E_OVERFLOW) {
+        r2 = sort_locked(c, false);
+        if (r2 == GSR_OK) r2 = blend_aux_locked(c, d_out, *aux);
+        c->split_state_hold = state;
+    }
+    c->depth_split = depth_split;
+    if (rc == GSR_E_OVERFLOW) {
+        // the view bookkeeping only
+        ctl.split_pm = c->split_pm;
+        ctl.split_floor = c->split_floor;
+        ctl.split_clean = c->split_clean;
+        ctl.split_spec = c->split_spec;
+        ctl.split_seen = c->split_seen;
+    }
+    split_ctl_restore(c, ctl);
+    if (rc != GSR_OK && rc != GSR_E_OVERFLOW) return rc;
+    return r2 ? r2 : rc;
 }
 
 // ------------------------------------------------------------------ frames in flight
@@ -1989,7 +2138,7 @@ extern "C" int gsr_get_tuning(gsr_context* c, int knob, int* value) {
     case GSR_TUNE_DEPTH_SPLIT: *value = c->depth_split; break;
     case GSR_TUNE_DEPTH_SPLIT_PERMILLE: *value = c->split_pm; break;
     case GSR_TUNE_DEPTH_SPLIT_UNSAT: *value = c->hstats ? (int)((const volatile Stats*)c->hstats)->split_unsat : 0; break;
-    case GSR_TUNE_DEPTH_SPLIT_STATE: *value = !c->split_frame ? 0 : !c->frame_key ? 1 : c->frame_spec ? 3 : 2; break;
+    case GSR_TUNE_DEPTH_SPLIT_STATE: *value = split_state(c); break;
     case GSR_TUNE_DEPTH_BUCKETS: *value = c->bucket_sort; break;
     case GSR_TUNE_BUCKET_ROWS: *value = c->fuse_rows; break;
     case GSR_TUNE_COL_CHUNK: *value = c->col_chunk; break;

@@ -143,6 +143,51 @@ int gsr_render(gsr_context* ctx, const void* d_scene, int layout, int64_t n,
                const gsr_camera* cam, int W, int H, int num_tile_x, int num_tile_y,
                int width_stride, int height_stride, float k, float* d_out, void* stream);
 
+/* Auxiliary render targets: gsr_render's frame with, besides (or instead of) the image,
+ * the accumulated alpha, the depth and up to GSR_AUX_MAX_FEATURES composited per-Gaussian
+ * feature channels.  The three-channel gsr_render path does not carry them: this entry
+ * point runs its own blend kernel over the same tile lists.
+ *
+ * For a pixel that composites splats i1, i2, ... (the decisions of render.cu:323-341), with
+ * T_j the transmittance before splat j and alpha_j its clamped alpha, every channel
+ * accumulates like a colour channel, acc = fma(v * alpha_j, T_j, acc) in list order, with
+ *   v = 1.0f                  alpha: the coverage sum alpha_j T_j = 1 - final T (rounded
+ *                             its own way), in [0, 1]; over a background B the composite is
+ *                             image + (1 - alpha) * B
+ *   v = -Z                    depth: Z is the splat's view-space z, the float behind its
+ *                             depth key (key = -Z * 1e6 saturated), so -Z is its positive
+ *                             distance along the view axis
+ *   v = d_features[f*n + i]   feature f of Gaussian i
+ * Depth (and the features) are the UN-NORMALISED sums: the expected depth of what the pixel
+ * composited is depth / alpha where alpha > 0, and the caller divides.
+ * d_out (may be NULL) receives the image gsr_render produces with the exact blend
+ * (GSR_TUNE_BLEND_EXP 0), bit for bit, whatever that knob is set to.
+ * All planes are W*H floats, planar, row 0 = bottom; pixels outside the covered area (the
+ * num_tile / stride arguments) and pixels no splat reaches are 0 in every plane.
+ *
+ * An aux frame always runs the exact blend in one phase: the depth split does not apply
+ * and its controller (split point, speculation, retry counters) is left exactly as it
+ * was.  Sorting, binning, overflow reporting (GSR_E_OVERFLOW, gsr_sync), the scene layouts
+ * (4D scenes render at gsr_set_time) and timing are gsr_render's; the aux blend is timed
+ * under GSR_STAGE_BLEND.  Aux frames write no diagnostics: the blend counters, the take
+ * map and the stamps keep the last non-aux frame's values.  Stream-ordered; allocates
+ * only when a high-water mark grows (workspace: n floats for the depth channel, 32 n bytes
+ * for more than four features).
+ * GSR_E_ARG, before any device work: every output NULL, nfeat outside
+ * [0, GSR_AUX_MAX_FEATURES], nfeat > 0 without d_features or d_feat_out, or aux NULL. */
+#define GSR_AUX_MAX_FEATURES 8
+typedef struct gsr_aux_targets {
+    float*       d_alpha;     /* W*H floats, or NULL */
+    float*       d_depth;     /* W*H floats, or NULL */
+    const float* d_features;  /* nfeat arrays of n floats, planar (feature f of Gaussian i at [f*n + i]);
+                                 NULL iff nfeat == 0 */
+    int          nfeat;       /* 0..GSR_AUX_MAX_FEATURES */
+    float*       d_feat_out;  /* nfeat*W*H floats planar; required iff nfeat > 0 */
+} gsr_aux_targets;
+int gsr_render_aux(gsr_context* ctx, const void* d_scene, int layout, int64_t n, const gsr_camera* cam,
+                   int W, int H, int num_tile_x, int num_tile_y, int width_stride, int height_stride,
+                   float k, float* d_out, const gsr_aux_targets* aux, void* stream);
+
 /* Offline camera path (config 4 on one GPU; the reference has no batch entry
  * point — it renders one frame per preprocessCUDAGaussians call, render.cu:871):
  * frame i renders cams[i] (at times[i] for 4D scenes; times may be NULL) into
@@ -372,7 +417,9 @@ enum {
                                         2 split by a depth threshold (near part sorted, far part sorted
                                         in phase B); 3 as 2 with no phase B queued (speculative: a frame
                                         that then leaves a block unsaturated is reported as
-                                        GSR_E_OVERFLOW and rendered again by the caller) */
+                                        GSR_E_OVERFLOW and rendered again by the caller).  Aux frames
+                                        (gsr_render_aux, always one phase) do not count: the knob keeps
+                                        the value of the frame before them */
     /* 27 reserved (removed, measured slower: the preprocess building the depth sort's pass-0
        histograms in 512-thread workgroups of 2048 Gaussians, pass 0 without its upsweep launch:
        preprocess 49.4 -> 60.3 us against the 5.7-us upsweep, -1.1 % one frame at a time and
