@@ -15,26 +15,25 @@ LIB = gaussianrenderer_amd/lib/libgsr.so
 OBJDIR = build/obj
 SRCDIR = gaussianrenderer_amd/csrc
 HDRS = include/gsr.h include/gsr_types.h include/gsr_detmath.h $(SRCDIR)/gsr_internal.h
+DEVHDRS = $(SRCDIR)/gsr_device.h
 
 all: $(LIB) oracle
 
-$(OBJDIR)/gsr_kernels.o: $(SRCDIR)/gsr_kernels.hip $(HDRS)
+# the kernel translation units (gfx950 device code + launch wrappers); a stage that gets a
+# file of its own is added here
+KOBJS = $(addprefix $(OBJDIR)/,gsr_kernels.o gsr_probes.o)
+
+$(OBJDIR)/%.o: $(SRCDIR)/%.hip $(HDRS) $(DEVHDRS)
 	mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
-$(OBJDIR)/gsr_runtime.o: $(SRCDIR)/gsr_runtime.cpp $(HDRS)
+$(OBJDIR)/%.o: $(SRCDIR)/%.cpp $(HDRS)
 	mkdir -p $(OBJDIR)
 	$(HIPCC) $(HOSTFLAGS) -x c++ -D__HIP_PLATFORM_AMD__ -c $< -o $@
 
-$(OBJDIR)/gsr_ply.o: $(SRCDIR)/gsr_ply.cpp $(HDRS)
-	mkdir -p $(OBJDIR)
-	$(HIPCC) $(HOSTFLAGS) -x c++ -D__HIP_PLATFORM_AMD__ -c $< -o $@
+$(OBJDIR)/gsr_gl.o: include/gsr_gl.h
 
-$(OBJDIR)/gsr_gl.o: $(SRCDIR)/gsr_gl.cpp $(HDRS) include/gsr_gl.h
-	mkdir -p $(OBJDIR)
-	$(HIPCC) $(HOSTFLAGS) -x c++ -D__HIP_PLATFORM_AMD__ -c $< -o $@
-
-$(LIB): $(OBJDIR)/gsr_kernels.o $(OBJDIR)/gsr_runtime.o $(OBJDIR)/gsr_ply.o $(OBJDIR)/gsr_gl.o
+$(LIB): $(KOBJS) $(OBJDIR)/gsr_runtime.o $(OBJDIR)/gsr_ply.o $(OBJDIR)/gsr_gl.o
 	mkdir -p $(dir $(LIB))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -ldl -Wl,-soname,libgsr.so
 
@@ -48,7 +47,7 @@ clean:
 .PHONY: all oracle clean
 
 # host-code ASan + UBSan build of libgsr.so and the oracle (tools/asan.mk; CPU tests only)
-asan: $(OBJDIR)/gsr_kernels.o
-	$(MAKE) -f tools/asan.mk -j $(JOBS)
+asan: $(KOBJS)
+	$(MAKE) -f tools/asan.mk -j $(JOBS) KOBJS="$(KOBJS)"
 
 .PHONY: asan

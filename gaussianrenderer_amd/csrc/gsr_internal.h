@@ -1,5 +1,5 @@
 // gsr_internal.h — shared between the host runtime (gsr_runtime.cpp) and the
-// gfx950 kernels (gsr_kernels.hip).  Not part of the public ABI.
+// gfx950 kernels (gsr_kernels.hip, gsr_probes.hip).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -123,7 +123,7 @@ struct BlendSplit {
                                       // GSR_FRAME_SPEC_MISS into the frame's validity word (nullable)
 };
 
-// ---- launch wrappers (gsr_kernels.hip) ----
+// ---- launch wrappers (gsr_kernels.hip; the probes' in gsr_probes.hip) ----
 hipError_t launch_aos_to_soa(const gsr_gaussian* aos, int64_t n, float* arrays, int64_t stride,
                              hipStream_t s);
 hipError_t launch_preprocess(const float* arrays, int64_t stride, int64_t n, const Frame& fr,

@@ -1,37 +1,12 @@
-// gsr_kernels.hip — gfx950 (CDNA4) kernels of the 3DGS rasterizer.
-//
-// Pipeline per frame (all stream-ordered, no host round trip):
-//   k_preprocess      one thread per Gaussian, SoA coalesced loads: cull + SH
-//                     colour + view/clip + 2D covariance + extent + AABB, writes a
-//                     64-B splat record, the (depth_key << 32 | index) item and
-//                     the tile rectangle (4 B packed on the binning path) [render.cu:472-786]
-//   radix passes      stable LSD sort of the N items by depth key (8-bit digits,
-//                     trailing identity passes skipped on the device); every pass
-//                     carries the packed rectangles, so they end in depth order
-//   k_bin_rows_*      tile binning, row pass: one item per covered tile row,
-//                     binned stably by row [render.cu:811-857, 788-809, 1099-1118]
-//   k_bin_cols_*      tile binning, column pass: one Gaussian index per covered
-//                     tile column, binned stably inside the row; tile ranges
-//   (k_emit_*, k_kv_*: pair emission + key-value tile sort, for grids over 256
-//                     tiles per axis)
-//   k_blend_w         one wave64 per 8x8 block, one pixel per lane; 64-record
-//                     batches culled against the block, survivors compacted into
-//                     LDS pair slots, two splats per iteration with packed math;
-//                     exact per-pixel early termination [render.cu:266-367]
+// gsr_kernels.hip — gfx950 (CDNA4) kernels of the 3DGS rasterizer (pipeline overview,
+// kernel by kernel: DESIGN.md section 9).
 //
 // Every float expression restates render.cu / math.cu in the same operation
 // order; the file is compiled with -ffp-contract=off so no FMA is formed
 // implicitly, and the transcendental functions come from gsr_detmath.h, so the
 // results are bit-identical to the CPU oracle (oracle/gsr_oracle.c).
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-
-#include <type_traits>
-
-#include "gsr_detmath.h"
-#include "gsr.h"
-#include "gsr_internal.h"
+// Shared wave / workgroup helpers: gsr_device.h; probes of no stage: gsr_probes.hip.
+#include "gsr_device.h"
 
 namespace gsr {
 
@@ -39,147 +14,6 @@ namespace {
 
 __constant__ float kShC0 = 0.28209479177387814f;      // render.cu:369-377
 __constant__ float kShC1 = 0.4886025119029199f;
-
-// Geometry kernels raise their waves' instruction-issue priority (s_setprio) above
-// the blend's: with frames in flight, a geometry wave that shares a SIMD with blend
-// waves would otherwise queue behind them for the VALU.  Issue priority only: no
-// preemption, no effect on a kernel running alone (+0.8 % frames/s in flight,
-// interleaved A/B of two builds: profiles/r02_ab_setprio.txt).
-#ifndef GSR_GEOM_PRIORITY
-#define GSR_GEOM_PRIORITY 3
-#endif
-#define GSR_GEOM_PRIO()                                                            \
-    do {                                                                           \
-        if (GSR_GEOM_PRIORITY > 0) __builtin_amdgcn_s_setprio(GSR_GEOM_PRIORITY); \
-    } while (0)
-
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
-
-// ------------------------------------------------------------------ helpers
-
-// Cross-lane moves on the DPP path (VALU) instead of ds_bpermute (the LDS crossbar,
-// one LDS round trip per step): a wave64 scan is six dependent VALU ops.  CDNA4 is a
-// GFX9 core, so row_bcast:15 / :31 and wave_shr:1 exist.  Lanes a control does not
-// reach (row start for row_shr, rows outside row_mask) read 0, the identity of every
-// scan below (add, unsigned max, or).
-template <int CTRL, int ROWM, bool BC>
-__device__ __forceinline__ uint32_t dpp_u32(uint32_t x) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, ROWM, 0xf, BC);
-}
-template <int CTRL, int ROWM, bool BC, typename T>
-__device__ __forceinline__ T dpp_mov(T x) {
-    if constexpr (sizeof(T) == 4) {
-        return (T)dpp_u32<CTRL, ROWM, BC>((uint32_t)x);
-    } else {
-        const uint64_t u = (uint64_t)x;
-        const uint32_t lo = dpp_u32<CTRL, ROWM, BC>((uint32_t)u), hi = dpp_u32<CTRL, ROWM, BC>((uint32_t)(u >> 32));
-        return (T)(((uint64_t)hi << 32) | lo);
-    }
-}
-struct OpAdd {
-    template <typename T>
-    __device__ T operator()(T a, T b) const { return a + b; }
-};
-struct OpMax {
-    __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return max(a, b); }
-};
-struct OpOr {
-    __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a | b; }
-};
-// Inclusive wave64 scan: Hillis-Steele inside each row of 16 lanes (row_shr 1, 2, 4, 8),
-// then row 0's total into row 1 and row 2's into row 3 (row_bcast:15), then rows 0-1's
-// into rows 2-3 (row_bcast:31).
-template <typename T, typename Op>
-__device__ __forceinline__ T wave_incl_scan(T x, Op op) {
-    x = op(x, dpp_mov<0x111, 0xf, true>(x));
-    x = op(x, dpp_mov<0x112, 0xf, true>(x));
-    x = op(x, dpp_mov<0x114, 0xf, true>(x));
-    x = op(x, dpp_mov<0x118, 0xf, true>(x));
-    x = op(x, dpp_mov<0x142, 0xa, false>(x));
-    x = op(x, dpp_mov<0x143, 0xc, false>(x));
-    return x;
-}
-// The value of the lane below (0 at lane 0): wave_shr:1.
-__device__ __forceinline__ uint32_t wave_shr1(uint32_t x) { return dpp_u32<0x138, 0xf, true>(x); }
-
-// Exclusive scan across a workgroup of NW waves (4 = 256 threads unless a kernel says
-// otherwise); `scratch` holds NW entries.  Contains two barriers; every thread of the
-// block must call it.
-template <typename T, int NW = 4>
-__device__ __forceinline__ T block_exclusive_scan(T v, T* scratch, T& total) {
-    const uint32_t lane = lane_id();
-    const uint32_t w = threadIdx.x >> 6;
-    const T x = wave_incl_scan(v, OpAdd{});
-    if (lane == 63) scratch[w] = x;
-    __syncthreads();
-    T pre = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < NW; k++) {
-        const T s = scratch[k];
-        if ((uint32_t)k < w) pre += s;
-        tot += s;
-    }
-    __syncthreads();
-    total = tot;
-    return pre + x - v;
-}
-
-// block_exclusive_scan without its trailing barrier: the caller barriers before `scratch`
-// is written again (and before anything it publishes from the result is read).
-template <typename T, int NW = 4>
-__device__ __forceinline__ T block_exclusive_scan_lead(T v, T* scratch, T& total) {
-    const uint32_t lane = lane_id();
-    const uint32_t w = threadIdx.x >> 6;
-    const T x = wave_incl_scan(v, OpAdd{});
-    if (lane == 63) scratch[w] = x;
-    __syncthreads();
-    T pre = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < NW; k++) {
-        const T s = scratch[k];
-        if ((uint32_t)k < w) pre += s;
-        tot += s;
-    }
-    total = tot;
-    return pre + x - v;
-}
-
-// Wave64-wide max / or (every lane gets the result: lane 63 of the inclusive scan).
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(v, OpMax{}), 63);
-}
-__device__ __forceinline__ uint32_t wave_or_u32(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(v, OpOr{}), 63);
-}
-
-// [begin, end) of workgroup g when n items are split over `groups` workgroups in
-// chunks that are multiples of `gran`.
-__device__ __forceinline__ void chunk_range(uint64_t n, int groups, int g, uint64_t gran,
-                                            uint64_t& b, uint64_t& e) {
-    uint64_t per = (n + (uint64_t)groups - 1) / (uint64_t)groups;
-    per = (per + gran - 1) / gran * gran;
-    b = per * (uint64_t)g;
-    if (b > n) b = n;
-    e = b + per;
-    if (e > n) e = n;
-}
-
-// Chunk handled by workgroup b of G when the chunks are dealt so that each XCD
-// takes one contiguous run of them (a bijection on [0, G); hardware dispatch sends
-// workgroup b to XCD b mod 8).  The partial cache lines at the seams between
-// consecutive chunks' output runs are then written through one L2.  Used by the
-// depth sort's downsweep at 16 items per thread (scenes of 4M+ Gaussians: config
-// 3 depth sort 173 -> 163 us); not by the binning scatters, whose chunks carry
-// uneven work (near splats cover more rows and columns) that contiguous runs would
-// pile onto one XCD (config 3 rows 100 -> 143 us, columns 143 -> 199 us;
-// profiles/r02_ab_xcd_chunks.txt).
-#ifndef GSR_XCD_DEPTH
-#define GSR_XCD_DEPTH 1   // 0: round-robin chunks in the depth downsweep too (A/B builds)
-#endif
-__device__ __forceinline__ int xcd_chunk(int b, int G) {
-    const int xcd = b & 7, q = G >> 3, r = G & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-}
 
 // --------------------------------------------------------------- AoS -> SoA
 
@@ -747,39 +581,6 @@ __global__ __launch_bounds__(256) void k_preprocess(const float* __restrict__ ar
     const SoaWg A{arr + i0, stride, 4u * threadIdx.x};
     (void)preprocess_one<T4D, SH3>(A, fr, rec, items, rect, packed, spans, tnow, rs, i);
 }
-
-// Lanes of the wave whose `bits`-bit digit equals this lane's, among the lanes in
-// `valid` (the wave64 stand-in for __match_any): one ballot per digit bit.  Per bit
-// 4 VALU: v_bfe_i32 (the bit as a 0 / -1 mask m), the ballot's v_cmp, and one
-// v_bitop3_b32 per mask half computing peers & ~(ballot ^ m) — truth table 0x90 for
-// (peers, ballot, m), index S0*4 + S1*2 + S2 (tools/microbench/bitop3_probe.hip) —
-// where the select-and-mask form compiles to 8.
-// (MAXB: compile-time bound on `bits`, so the loop unrolls; bits <= MAXB.)
-template <int MAXB>
-__device__ __forceinline__ uint64_t match_peers(uint32_t d, bool valid, int bits) {
-    const uint64_t v = __ballot(valid);
-    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-#pragma unroll
-    for (int bit = 0; bit < MAXB; bit++) {
-        if (bit >= bits) break;
-        const int m = __builtin_amdgcn_sbfe((int)d, bit, 1);
-        const uint64_t bm = __ballot(m != 0);
-        lo = __builtin_amdgcn_bitop3_b32(lo, (uint32_t)bm, (uint32_t)m, 0x90);
-        hi = __builtin_amdgcn_bitop3_b32(hi, (uint32_t)(bm >> 32), (uint32_t)m, 0x90);
-    }
-    return ((uint64_t)hi << 32) | lo;
-}
-
-// Stable in-wave ranks from returning LDS atomics (template flag RA, runtime knob
-// GSR_TUNE_RANK_ATOMIC): atomicAdd(&count[digit], 1) from one wave64 instruction
-// returns the old values in LANE order when several lanes hit one address — measured
-// on gfx950 with no exception in 1.5e10 lane-operations over uniform, skewed, run and
-// interleaved digit patterns (tools/microbench/lds_atomic_order.hip) — so the returned
-// value is the element's stable rank among the wave's earlier elements of its digit:
-// one LDS op instead of ballot matching (4 VALU per digit bit, match_peers).  The ISA
-// does not document that order, so the runtime only takes RA = true after
-// k_rank_order_check (below) has found it on the device in this process; otherwise,
-// or with the knob at 0, every kernel ranks with ballots (RA = false).
 
 // ------------------------------------------------------------------ radix sort
 //
@@ -3478,13 +3279,6 @@ __global__ __launch_bounds__(256) void k_part_scatter(const uint64_t* __restrict
 // ------------------------------------------------------------------ blend
 
 
-// Bijective XCD-aware remap: blocks that share an XCD (b % 8) get one
-// contiguous run of tiles, so neighbouring tiles' shared splats hit one L2.
-__device__ __forceinline__ int xcd_remap(int b, int nb) {
-    const int xcd = b & 7, q = nb >> 3, r = nb & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-}
-
 typedef float f2 __attribute__((ext_vector_type(2)));
 
 // Packed product with the HIGH half of the second operand broadcast to both lanes,
@@ -3635,6 +3429,23 @@ __device__ __forceinline__ uint64_t box_mask(uint32_t d) {
 // a mix of their Gaussian indices (the oracle's orc_render_takes computes the same).
 __device__ __forceinline__ uint32_t take_mix(uint32_t g) { return (g + 1u) * 2654435761u; }
 
+// The block L (tile-major index: tile << 2 | sub-block) of workgroup vb of k_blend_w and
+// k_blend_aux; false for a padding workgroup.  bands > 1: band j of B consecutive blocks goes
+// to XCD j mod 8; else one contiguous run of blocks per XCD (xcd_chunk).  (k_blend_w's comment.)
+__device__ __forceinline__ bool blend_block_index(int vb, int ntiles, int bands, int& L) {
+    if (bands > 1) {
+        const int nu = 4 * ntiles;
+        const int B = (nu + 8 * bands - 1) / (8 * bands);
+        const int k = vb >> 3;
+        L = ((k / B) * 8 + (vb & 7)) * B + k % B;
+        if (L >= nu) return false;
+    } else {
+        if (vb >= ntiles * 4) return false;
+        L = xcd_chunk(vb, ntiles * 4);
+    }
+    return true;
+}
+
 // One 8x8 pixel block (bx, by) blended by one wave over the tile list
 // idx[beg, end), using the wave's private LDS slice wP (32 pair slots).
 //
@@ -3712,6 +3523,7 @@ __device__ __forceinline__ uint64_t blend_block(const uint32_t* __restrict__ idx
     for (uint32_t base = beg; base < end && alive; base += 64) {
         const uint32_t cnt = min(64u, end - base);
         // ---- cull + lane masks + compaction (lane = record) ----
+        // (k_blend_aux holds a copy of this cull and of the load / prefetch around it: keep them identical)
         // pixels not yet saturated at the batch start: T only decreases, so a record
         // whose in-box pixels are all saturated here can never be taken in this batch
         const uint64_t live_b = __ballot(!(T < 1e-3f));
@@ -4024,7 +3836,7 @@ __device__ __forceinline__ uint64_t blend_block(const uint32_t* __restrict__ idx
 // consecutive blocks and band j goes to XCD j mod 8, so each XCD's L2 serves runs
 // of neighbouring tiles while heavy and light image regions spread over all XCDs;
 // padding workgroups past the last block exit.  bands <= 1: one contiguous run of
-// blocks per XCD (xcd_remap).
+// blocks per XCD (xcd_chunk).
 // FX: fast-exp blend; a block it cannot vouch for is blended again exactly by the
 // same wave (counters[8] blocks, counters[9] suspect pixels, with diagnostics).
 // STAMPS (timeline diagnostics, no counters): counters[2 * g] = start of the
@@ -4062,16 +3874,7 @@ __global__ __launch_bounds__(64, 8) void k_blend_w(const uint32_t* __restrict__ 
         if (g == 0u) return;
     }
     int L;
-    if (bands > 1) {
-        const int nu = 4 * ntiles;
-        const int B = (nu + 8 * bands - 1) / (8 * bands);
-        const int k = vb >> 3;
-        L = ((k / B) * 8 + (vb & 7)) * B + k % B;
-        if (L >= nu) return;
-    } else {
-        if (vb >= ntiles * 4) return;
-        L = xcd_remap(vb, ntiles * 4);
-    }
+    if (!blend_block_index(vb, ntiles, bands, L)) return;
     if (SPLIT == 2 && sp.bflag[L] == 0u) return;   // saturated in phase A: its pixels are final
     const int tile = L >> 2, sub = L & 3;
     const int tx = tile % tiles_x, ty = tile / tiles_x;
@@ -4215,16 +4018,7 @@ __global__ __launch_bounds__(64, NF > 4 ? 6 : 8) void k_blend_aux(const uint32_t
     const int ntiles = tiles_x * tiles_y;
     const int vb = (int)blockIdx.x;
     int L;
-    if (bands > 1) {
-        const int nu = 4 * ntiles;
-        const int B = (nu + 8 * bands - 1) / (8 * bands);
-        const int k = vb >> 3;
-        L = ((k / B) * 8 + (vb & 7)) * B + k % B;
-        if (L >= nu) return;
-    } else {
-        if (vb >= ntiles * 4) return;
-        L = xcd_remap(vb, ntiles * 4);
-    }
+    if (!blend_block_index(vb, ntiles, bands, L)) return;
     const int tile = L >> 2, sub = L & 3;
     const int tx = tile % tiles_x, ty = tile / tiles_x;
     const int lane = (int)(threadIdx.x & 63u);
@@ -4256,8 +4050,8 @@ __global__ __launch_bounds__(64, NF > 4 ? 6 : 8) void k_blend_aux(const uint32_t
     bool alive = __ballot(!(T < 1e-3f)) != 0ull;
     for (uint32_t base = beg; base < end && alive; base += 64) {
         const uint32_t cnt = min(64u, end - base);
-        // ---- cull (lane = record): blend_block's, AABB vs block, the live-pixel filter,
-        // then the ellipse-vs-block test ----
+        // ---- cull (lane = record): a copy of blend_block's, as are the load / prefetch around it
+        // (keep them identical): AABB vs block, the live-pixel filter, the ellipse-vs-block test ----
         const uint64_t live_b = __ballot(!(T < 1e-3f));
         bool hit;
         uint32_t dsc;
@@ -4430,87 +4224,6 @@ __global__ void k_gather_lwg(const gsr_lwg* __restrict__ in, const uint64_t* __r
     out[i] = in[r];
 }
 
-// ------------------------------------------------------------------ rank-order self-check
-//
-// The RA rank path (match_peers' comment) relies on same-address ds_add_rtn_u32 lanes
-// of one wave64 instruction returning the old values in lane order.  The runtime runs
-// this check once per process and device before it uses that path: every wave of
-// 256-thread workgroups (per-wave counters, as in the sort and binning kernels) ranks
-// digits from 24 patterns — 1 to 256 distinct digits; uniform, a third of the lanes on
-// one digit, runs of 16 lanes, interleaved; ~1/8 of the lanes idle — by returning
-// atomics and by ballot matching, and counts the lanes where the two differ.
-__device__ __forceinline__ uint32_t rank_check_hash(uint32_t x) {
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
-__global__ __launch_bounds__(256) void k_rank_order_check(uint32_t seed, int iters,
-                                                           unsigned long long* __restrict__ out) {
-    __shared__ uint32_t cnt[4][256];
-    const uint32_t t = threadIdx.x, w = t >> 6, lane = t & 63u;
-#pragma unroll
-    for (int k = 0; k < 4; k++) cnt[k][t] = 0;
-    __syncthreads();
-    const uint64_t lt = lane ? (~0ull >> (64 - lane)) : 0ull;
-    unsigned long long bad = 0, ops = 0;
-    for (int pat = 0; pat < 24; pat++) {
-        const int skew = pat / 6;
-        constexpr uint32_t kDigits[6] = {1u, 2u, 4u, 16u, 128u, 256u};
-        const uint32_t ndig = kDigits[pat % 6];
-        for (int it = 0; it < iters; it++) {
-            const uint32_t h = rank_check_hash(seed ^ (blockIdx.x * 7919u + (uint32_t)(pat * iters + it) * 104729u +
-                                                       lane * 31u + w * 1000003u));
-            uint32_t d = h % ndig;
-            if (skew == 1) d = (h >> 8) % 3u == 0u ? 0u : d;
-            if (skew == 2) d = (lane >> 4) % ndig;
-            if (skew == 3) d = ((h >> 4) & 1u) ? (lane * 5u) % ndig : 1u % ndig;
-            const bool valid = ((h >> 20) & 7u) != 0u;
-            const uint64_t peers = match_peers<8>(d, valid, 8);
-            uint32_t before = 0;
-            if (valid) before = cnt[w][d];
-            __builtin_amdgcn_wave_barrier();
-            uint32_t got = 0;
-            if (valid) got = atomicAdd(&cnt[w][d], 1u);
-            __builtin_amdgcn_wave_barrier();
-            if (valid) {
-                bad += got != before + (uint32_t)__popcll(peers & lt);
-                ops++;
-            }
-        }
-    }
-    // wave sums, one device atomic per wave
-    for (int o = 32; o >= 1; o >>= 1) {
-        bad += __shfl_xor(bad, o, 64);
-        ops += __shfl_xor(ops, o, 64);
-    }
-    if (lane == 0) {
-        atomicAdd(&out[0], ops);
-        atomicAdd(&out[1], bad);
-    }
-}
-
-// ------------------------------------------------------------------ math probe
-
-__global__ void k_math_probe(const float* __restrict__ in, int n, float* __restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float x = in[2 * i], y = in[2 * i + 1];
-    float* o = out + 9 * i;
-    o[0] = gsr_expf(x);
-    o[8] = gsr_blend_expf(x);
-    o[1] = gsr_sinf(x);
-    o[2] = gsr_cosf(x);
-    o[3] = gsr_atan2f(x, y);
-    o[4] = sqrtf(x);
-    o[5] = x / y;
-    o[6] = roundf(x);
-    o[7] = __int_as_float(gsr_f2i_sat(x * 1000.0f));
-}
-
 // Exhaustive checks behind the blend's exp (gsr_exp_probe).  Over every float key k
 // in [key_lo, key_hi): viol[0] counts gsr_blend_expf(x_k) > gsr_blend_expf(x_k+1)
 // (monotonicity of the exact exp, which makes the alpha test a threshold on its
@@ -4555,15 +4268,6 @@ __global__ void k_xs_probe(const float* __restrict__ op, int n, float* __restric
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = gsr_alpha_take_min_x(op[i]);
 }
-
-// f(std::true_type{}) or f(std::false_type{}): a runtime bool as a template argument of the
-// launches in the generic lambda f.
-template <typename F>
-inline auto with_bool(bool b, F&& f) {
-    return b ? f(std::true_type{}) : f(std::false_type{});
-}
-
-inline int grid_for(int64_t n, int block) { return (int)((n + block - 1) / block); }
 
 }  // namespace
 
@@ -4884,6 +4588,17 @@ hipError_t launch_kv_pass(const void* keys_in, const uint32_t* vals_in, void* ke
     return hipGetLastError();
 }
 
+// The grid of both blends (blend_block_index): `bands` bands of band_tiles tiles per XCD, dealt
+// round-robin; ng is padded to whole rounds.  Too small for two rounds: one run per XCD (bands 1).
+static void blend_grid(int nt, int band_tiles, int& bands, int& ng) {
+    bands = 1;
+    ng = 4 * nt;
+    if (band_tiles > 0 && (nt + 8 * band_tiles - 1) / (8 * band_tiles) > 1) {
+        bands = (nt + 8 * band_tiles - 1) / (8 * band_tiles);
+        ng = 8 * bands * ((4 * nt + 8 * bands - 1) / (8 * bands));
+    }
+}
+
 hipError_t launch_blend(const uint32_t* idx, const uint2* ranges, const uint4* rec, const Frame& fr,
                         float* out, unsigned long long* consumed, bool stamps, int band_tiles, int blend_exp,
                         hipStream_t s, const BlendSplit* split) {
@@ -4893,14 +4608,8 @@ hipError_t launch_blend(const uint32_t* idx, const uint2* ranges, const uint4* r
     const float band0 = blend_exp == 2 ? 1.0f : kFxBand0;
     const int nt = fr.tiles_x * fr.tiles_y;
     if (nt <= 0) return hipSuccess;
-    // bands of band_tiles tiles (4 blocks each) dealt round-robin to the 8 XCDs; the
-    // grid is padded to whole rounds of bands.  Images too small for two rounds:
-    // one contiguous run per XCD.
-    int bands = 1, ng = 4 * nt;
-    if (band_tiles > 0 && (nt + 8 * band_tiles - 1) / (8 * band_tiles) > 1) {
-        bands = (nt + 8 * band_tiles - 1) / (8 * band_tiles);          // bands per XCD
-        ng = 8 * bands * ((4 * nt + 8 * bands - 1) / (8 * bands));
-    }
+    int bands, ng;
+    blend_grid(nt, band_tiles, bands, ng);
     const int phase = split ? split->phase : 0;
     if (phase < 0 || phase > 2 || (phase && (fast_exp || stamps || !split->tbuf || !split->bflag || !split->gate)))
         return hipErrorInvalidValue;
@@ -4951,12 +4660,8 @@ hipError_t launch_blend_aux(const uint32_t* idx, const uint2* ranges, const uint
         return hipErrorInvalidValue;
     const int nt = fr.tiles_x * fr.tiles_y;
     if (nt <= 0) return hipSuccess;
-    // the grid of launch_blend: bands of band_tiles tiles dealt round-robin to the 8 XCDs
-    int bands = 1, ng = 4 * nt;
-    if (band_tiles > 0 && (nt + 8 * band_tiles - 1) / (8 * band_tiles) > 1) {
-        bands = (nt + 8 * band_tiles - 1) / (8 * band_tiles);
-        ng = 8 * bands * ((4 * nt + 8 * bands - 1) / (8 * bands));
-    }
+    int bands, ng;
+    blend_grid(nt, band_tiles, bands, ng);
     if (nfeat > 4 && n > 0)
         hipLaunchKernelGGL(k_aux_pack, dim3(grid_for(n, 256)), dim3(256), 0, s, features, n, nfeat, pack);
     const AuxIO io{out, alpha, depth, feat_out, features, pack, depth ? z : nullptr, n, nfeat};
@@ -5002,30 +4707,6 @@ hipError_t launch_items_from_lwg(const gsr_lwg* rec, const uint64_t* src_perm, u
 hipError_t launch_gather_lwg(const gsr_lwg* in, const uint64_t* stage1, const uint64_t* stage2, uint32_t n,
                              gsr_lwg* out, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_gather_lwg, dim3((n + 255) / 256), dim3(256), 0, s, in, stage1, stage2, n, out);
-    return hipGetLastError();
-}
-
-hipError_t rank_order_check(unsigned long long* lane_ops, unsigned long long* mismatches) {
-    unsigned long long* d = nullptr;
-    unsigned long long h[2] = {0, 0};
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), sizeof h);
-    if (e != hipSuccess) return e;
-    e = hipMemset(d, 0, sizeof h);
-    // 1,024 workgroups (4 per CU) x 24 patterns x 8 iterations: ~44M lane-operations, well under 1 ms
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_rank_order_check, dim3(1024), dim3(256), 0, nullptr, 0x9E3779B9u, 8, d);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    *lane_ops = h[0];
-    *mismatches = h[1];
-    return e;
-}
-
-hipError_t launch_math_probe(const float* in, int n, float* out, hipStream_t s) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_math_probe, dim3(grid_for(n, 256)), dim3(256), 0, s, in, n, out);
     return hipGetLastError();
 }
 

@@ -551,7 +551,7 @@ int realloc_dev(T** p, size_t count) {
     return GSR_OK;
 }
 
-// ---- rank-order self-check, once per process and device (gsr_kernels.hip
+// ---- rank-order self-check, once per process and device (gsr_probes.hip
 // k_rank_order_check).  The sort and binning kernels rank with returning LDS atomics
 // only on a gfx950 device that returned every same-address lane in lane order.
 struct RankCheck {

@@ -2,8 +2,9 @@
 # sanitizers"): AddressSanitizer + UndefinedBehaviorSanitizer on the HOST code only.
 #
 #   build/asan/libgsr.so      libgsr.so with the host runtime, the PLY parser and the GL
-#                             interop instrumented (the gfx950 kernels object is the
-#                             normal one: device code is never sanitized here)
+#                             interop instrumented (the gfx950 kernel objects, KOBJS from
+#                             the top-level Makefile, are the normal ones: device code
+#                             is never sanitized here)
 #   build/asan/liboracle.so   the C oracle, instrumented
 #
 # Both use clang's sanitizer runtime (ROCm's LLVM), so one preloaded runtime serves a
@@ -14,6 +15,8 @@ HIPCC ?= $(ROCM)/bin/hipcc
 CLANG ?= $(ROCM)/lib/llvm/bin/clang
 ARCH ?= gfx950
 OUT = build/asan
+# the normal kernel objects; the top-level `make asan` builds them first and passes its list
+KOBJS ?= build/obj/gsr_kernels.o build/obj/gsr_probes.o
 SRC = gaussianrenderer_amd/csrc
 # host-only compiles (-x c++): the sanitizer flags apply to host code only
 SAN = -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
@@ -28,7 +31,7 @@ $(OUT)/%.o: $(SRC)/%.cpp $(HDRS)
 	mkdir -p $(OUT)
 	$(HIPCC) $(HOSTFLAGS) $(SAN) -x c++ -c $< -o $@
 
-$(OUT)/libgsr.so: build/obj/gsr_kernels.o $(OUT)/gsr_runtime.o $(OUT)/gsr_ply.o $(OUT)/gsr_gl.o
+$(OUT)/libgsr.so: $(KOBJS) $(OUT)/gsr_runtime.o $(OUT)/gsr_ply.o $(OUT)/gsr_gl.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
 	    -shared-libsan -o $@ $^ -ldl -Wl,-soname,libgsr.so
 
