@@ -21,7 +21,7 @@ from ctypes import byref, c_float, c_int, c_int64, c_void_p
 import numpy as np
 
 from . import _native
-from ._native import (AUX_MAX_FEATURES, AuxTargets, Camera, GsrError, LAYOUT_AOS, LAYOUT_SCENE_BLOCK, LAYOUT_SCENE_BLOCK_4D,
+from ._native import (AUX_MAX_FEATURES, AuxTargets, CONTRIB_WEIGHT_ONE, Camera, ContribTargets, GsrError, LAYOUT_AOS, LAYOUT_SCENE_BLOCK, LAYOUT_SCENE_BLOCK_4D,
                       LAYOUT_SCENE_BLOCK_SH3, NUM_STAGES, PLY_SH3, PLY_TYPED, SCENE4D_NARRAYS, SCENE_NARRAYS,
                       SCENE_SH3_NARRAYS,
                       SPLAT_RECORD_BYTES, STAGES, TILE_PX, check, lib)
@@ -30,6 +30,7 @@ __all__ = [
     "Camera", "GsrError", "Renderer", "Scene", "TilingInformation", "make_camera", "orbit",
     "loadGaussianCudaFromPly", "preprocessCUDAGaussians", "read_ply", "write_synthetic_ply",
     "SPLAT_DTYPE", "STAGES", "TILE_PX", "lib", "AUX_MAX_FEATURES", "DisplayTarget", "display_gl_current", "preprocessCUDAGaussiansGL",
+    "CONTRIB_WEIGHT_ONE", "ContribTargets",
 ]
 
 # gsr_read_splats record (include/gsr.h).
@@ -331,6 +332,33 @@ class Renderer:
                                   t.width_stride, t.height_stride, k, out_ptr or None, byref(aux), stream or None)
         if rc not in (_native.GSR_OK, _native.GSR_E_OVERFLOW):
             raise GsrError(rc, "gsr_render_aux")
+        return rc
+
+    def render_contrib(self, scene, cam: Camera, W: int, H: int, count_ptr: int | None = None,
+                       weight_ptr: int | None = None, max_ptr: int | None = None, id_ptr: int | None = None,
+                       k: float = 3.0, tiling=None, stream: int = 0, layout: int = LAYOUT_SCENE_BLOCK,
+                       n: int | None = None, time: float | None = None) -> int:
+        """Enqueue one frame of contribution statistics (gsr_render_contrib, include/gsr.h), each
+        a device buffer or None.  Per Gaussian, ACCUMULATED (zero them once; every frame adds):
+        count_ptr n uint32, the pixels that composited it; weight_ptr n uint64, the sum of their
+        blend weights in fixed point (CONTRIB_WEIGHT_ONE = 1.0); max_ptr n uint32, the float
+        bits of its largest weight.  id_ptr W*H int32, overwritten: per pixel the composited
+        Gaussian with the largest weight, -1 for none.  A frame that overflows adds nothing.
+        Same returns as render()."""
+        if not (count_ptr or weight_ptr or max_ptr or id_ptr):
+            raise ValueError("render_contrib: no output requested")
+        ptr = scene.ptr if isinstance(scene, Scene) else int(scene)
+        n = scene.n if n is None else n
+        if isinstance(scene, Scene) and layout == LAYOUT_SCENE_BLOCK:
+            layout = scene.layout
+        if time is not None:
+            self.set_time(time)
+        t = tiling or TilingInformation(1, 1, H, W)
+        out = ContribTargets(count_ptr or None, weight_ptr or None, max_ptr or None, id_ptr or None)
+        rc = lib().gsr_render_contrib(self.ctx, ptr, layout, n, byref(cam), W, H, t.num_tile_x, t.num_tile_y,
+                                      t.width_stride, t.height_stride, k, byref(out), stream or None)
+        if rc not in (_native.GSR_OK, _native.GSR_E_OVERFLOW):
+            raise GsrError(rc, "gsr_render_contrib")
         return rc
 
     def set_frames_in_flight(self, frames: int):

@@ -101,6 +101,20 @@ class AuxTargets(ctypes.Structure):
     ]
 
 
+CONTRIB_WEIGHT_ONE = 1 << 24   # GSR_CONTRIB_WEIGHT_ONE
+
+
+class ContribTargets(ctypes.Structure):
+    """``gsr_contrib_targets`` (include/gsr.h): the outputs of gsr_render_contrib."""
+
+    _fields_ = [
+        ("d_count", c_void_p),
+        ("d_weight", c_void_p),
+        ("d_max", c_void_p),
+        ("d_id", c_void_p),
+    ]
+
+
 # (name, restype, argtypes) for every symbol of include/gsr.h and include/gsr_gl.h.
 SIGNATURES = [
     ("preprocessCUDAGaussians", None,
@@ -125,6 +139,8 @@ SIGNATURES = [
                            c_int, c_int, c_float, c_void_p, c_void_p]),
     ("gsr_render_aux", c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(Camera), c_int, c_int, c_int, c_int,
                                c_int, c_int, c_float, c_void_p, POINTER(AuxTargets), c_void_p]),
+    ("gsr_render_contrib", c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(Camera), c_int, c_int, c_int, c_int,
+                                   c_int, c_int, c_float, POINTER(ContribTargets), c_void_p]),
     ("gsr_render_path", c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(Camera), c_void_p, c_int, c_int,
                                 c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     ("gsr_render_path_ex", c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(Camera), c_void_p, c_int, c_int,

@@ -217,6 +217,16 @@ hipError_t launch_blend_aux(const uint32_t* idx, const uint2* ranges, const uint
                             float* out, float* alpha, float* depth, const float* z, const float* features,
                             int64_t n, int nfeat, float* feat_out, float4* pack, int band_tiles,
                             hipStream_t s);
+// Contribution statistics (gsr_render_contrib; k_blend_contrib): the exact blend's decisions
+// over the same lists with k_blend_aux's schedule, no colours.  Per Gaussian i (nullable
+// each, n words, ACCUMULATED with integer atomics, one per statistic per wave and surviving
+// splat): count += pixels that composited i, weight += their rint(w 2^24), wmax = max(wmax,
+// float bits of w), w = fma(alpha, T, 0).  id (nullable, W*H words, overwritten): the
+// composited Gaussian with the largest w per pixel, -1 for none.  overflow: the frame's
+// Stats::overflow word; when it is non-zero the kernel returns without touching anything.
+hipError_t launch_blend_contrib(const uint32_t* idx, const uint2* ranges, const uint4* rec, const Frame& fr,
+                                uint32_t* count, unsigned long long* weight, uint32_t* wmax, int32_t* id,
+                                const uint32_t* overflow, int band_tiles, hipStream_t s);
 // Stable partition of the preprocess items: visible first, culled last (both in
 // index order), visible count into *n_live; culled tail to out only, with dead
 // rects in srect (gsr_kernels.hip "live partition").  counts: groups words.

@@ -4190,6 +4190,194 @@ __global__ __launch_bounds__(64, NF > 4 ? 6 : 8) void k_blend_aux(const uint32_t
     }
 }
 
+// Where k_blend_contrib adds its per-Gaussian statistics and writes its id plane (nullable
+// each), and the frame's overflow word (Stats::overflow).
+struct ContribIO {
+    uint32_t* count;
+    unsigned long long* weight;
+    uint32_t* wmax;
+    int32_t* id;
+    const uint32_t* overflow;
+};
+
+constexpr int kContribCount = 1, kContribWeight = 2, kContribMax = 4, kContribId = 8;
+
+// Per-Gaussian contribution statistics and the id plane (gsr_render_contrib): k_blend_aux's
+// schedule — one wave64 per 8x8 block, one-wave workgroups, the same block -> workgroup
+// mapping and tile lists, the same 64-record batches, prefetch and conservative cull — and,
+// for every survivor, the exact one-splat step (gsr_blend_md2, gsr_blend_expf, selects), so
+// each pixel takes the decisions of render.cu:323-341.  No colours: a lane keeps its T, the
+// largest weight w = fma(alpha, T, 0) it composited and that splat's Gaussian index.
+//
+// A scatter, not a composite: per survivor the wave reduces its taking lanes to one triple
+// {popcount of the take ballot, sum of rint(w 2^24), max of w's float bits} (scalar values)
+// and parks it in the survivor's RECORD lane, which still holds the Gaussian index in a
+// register (saved before the prefetch overwrites cidx).  After the batch's loop every
+// survivor lane with a non-zero count issues its own atomics: at most one per statistic per
+// (wave, surviving splat), 64 distinct addresses per instruction, never one per pixel.  All
+// three reductions are integer (the weights in fixed point: 64 values below 2^24 fit 32 bits
+// in the wave, the global sum is 64-bit), so the totals do not depend on the order in which
+// waves, frames or streams add to them.
+//
+// A frame whose overflow word is set (truncated tile lists or an incomplete depth order)
+// returns at once: it adds nothing, and the caller renders it again.
+//
+// Survivor k's slot in the wave's LDS slice (8 dwords, read with wave-uniform addresses):
+//   [0] cx [1] cy [2] a [3] b | [4] c [5] e [6] opacity [7] unused
+// WHAT: the kContrib* bits of the outputs wanted; the others' reductions drop out.
+template <int WHAT>
+__global__ __launch_bounds__(64, 8) void k_blend_contrib(const uint32_t* __restrict__ idx,
+                                                         const uint2* __restrict__ ranges,
+                                                         const uint4* __restrict__ rec, int tiles_x, int tiles_y,
+                                                         int W, int H, int cover_w, int cover_h, int bands,
+                                                         ContribIO io) {
+    constexpr bool CNT = (WHAT & kContribCount) != 0, WGT = (WHAT & kContribWeight) != 0;
+    constexpr bool MAXW = (WHAT & kContribMax) != 0, ID = (WHAT & kContribId) != 0;
+    constexpr bool STATS = CNT || WGT || MAXW;
+    __shared__ float4 sP[64 * 2];
+    if (*io.overflow) return;   // uniform: an incomplete frame adds nothing
+    const int ntiles = tiles_x * tiles_y;
+    const int vb = (int)blockIdx.x;
+    int L;
+    if (!blend_block_index(vb, ntiles, bands, L)) return;
+    const int tile = L >> 2, sub = L & 3;
+    const int tx = tile % tiles_x, ty = tile / tiles_x;
+    const int lane = (int)(threadIdx.x & 63u);
+    const uint2 rr = ranges[tile];                          // {~start, end}, zero = empty
+    const uint32_t beg = rr.y ? ~rr.x : 0u, end = rr.y;
+    const int bx = tx * GSR_TILE_PX + (sub & 1) * 8, by = ty * GSR_TILE_PX + (sub >> 1) * 8;
+    const float4* wP4 = sP;
+
+    const int px = bx + (lane & 7), py = by + (lane >> 3);
+    const bool inside = px < cover_w && py < cover_h;
+    const float fpx = (float)px, fpy = (float)py;
+    // pixels outside the covered area start saturated and composite nothing (blend_block)
+    float T = inside ? 1.0f : 0.0f;
+    float best_w = 0.0f;
+    int32_t best_i = -1;
+
+    uint4 ra = make_uint4(0, 0, 0, 0), rb = ra, rc = ra, rd = ra;
+    uint32_t nidx = 0, cidx = 0;
+    if (beg + lane < end) {
+        cidx = idx[beg + lane];
+        const uint4* R = rec + 4 * (uint64_t)cidx;
+        ra = R[0];
+        rb = R[1];
+        rc = R[2];
+        rd = R[3];
+    }
+    if (beg + 64 + lane < end) nidx = idx[beg + 64 + lane];
+    bool alive = __ballot(!(T < 1e-3f)) != 0ull;
+    for (uint32_t base = beg; base < end && alive; base += 64) {
+        const uint32_t cnt = min(64u, end - base);
+        // ---- cull (lane = record): a copy of blend_block's, as are the load / prefetch around it
+        // (keep them identical): AABB vs block, the live-pixel filter, the ellipse-vs-block test ----
+        const uint64_t live_b = __ballot(!(T < 1e-3f));
+        bool hit;
+        uint32_t dsc;
+        {
+            const bool valid = (uint32_t)lane < cnt;
+            const int xmin = (int)(rc.z & 0xffffu), xmax = (int)(rc.z >> 16);
+            const int ymin = (int)(rc.w & 0xffffu), ymax = (int)(rc.w >> 16);
+            const bool box_hit = valid & !((xmax < bx) | (xmin > bx + 7) | (ymax < by) | (ymin > by + 7));
+            const float cx = __uint_as_float(rc.x), cy = __uint_as_float(rc.y);
+            const float a = __uint_as_float(ra.x), b = __uint_as_float(ra.y);
+            const float c = __uint_as_float(ra.z), e = __uint_as_float(ra.w);
+            const int x0 = max(xmin - bx, 0), x1 = min(xmax - bx, 7);
+            const int y0 = max(ymin - by, 0), y1 = min(ymax - by, 7);
+            const float dx0 = (float)(bx + x0) - cx, dx1 = (float)(bx + x1) - cx;
+            const float dy0 = (float)(by + y0) - cy, dy1 = (float)(by + y1) - cy;
+            // box descriptor (box_mask); shift counts masked to the hardware's: only lanes
+            // outside the box can have them out of range, and their results are discarded
+            const uint32_t colb = (0xffu >> ((uint32_t)(7 - (x1 - x0)) & 31u)) << ((uint32_t)x0 & 31u);
+            const uint32_t rsh = (uint32_t)(56 - 8 * (y1 - y0)) & 63u, lsh = (uint32_t)(8 * y0) & 63u;
+            dsc = colb | (rsh << 8) | (lsh << 16);
+            const uint64_t rows = (~0ull >> rsh) << lsh;
+            const uint32_t rep = __builtin_amdgcn_perm(colb, colb, 0u);   // colb in every byte
+            const uint64_t lrows = rows & live_b;
+            const float S = __uint_as_float(rd.w);
+            const float M = fmaxf(fmaxf(fabsf(dx0), fabsf(dx1)), fmaxf(fabsf(dy0), fabsf(dy1)));
+            const float SMM = S * M * M;
+            hit = box_hit & ((((uint32_t)lrows | (uint32_t)(lrows >> 32)) & rep) != 0u) &
+                  block_may_reach(a, b, c, e, __uint_as_float(rd.y), __uint_as_float(rd.z), dx0, dx1, dy0, dy1,
+                                  SMM, block_cut(__uint_as_float(rd.x)));
+        }
+        // ---- survivors, compacted in list order ----
+        const uint64_t m = __ballot(hit);
+        const uint32_t k_l = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        if (hit) {
+            float4* S4 = sP + k_l * 2;
+            S4[0] = make_float4(__uint_as_float(rc.x), __uint_as_float(rc.y), __uint_as_float(ra.x),
+                                __uint_as_float(ra.y));
+            S4[1] = make_float4(__uint_as_float(ra.z), __uint_as_float(ra.w), __uint_as_float(rb.x), 0.0f);
+        }
+        const uint32_t gidx = cidx;   // this batch's Gaussian index of record `lane`
+        // ---- prefetch: records of batch k+1, indices of batch k+2 ----
+        if (base + 64 + lane < end) {
+            cidx = nidx;
+            const uint4* R = rec + 4 * (uint64_t)nidx;
+            ra = R[0];
+            rb = R[1];
+            rc = R[2];
+            rd = R[3];
+        }
+        if (base + 128 + lane < end) nidx = idx[base + 128 + lane];
+        // ---- the exact one-splat step over the survivors (render.cu:329-340) ----
+        uint32_t p_cnt = 0, p_sum = 0, p_max = 0;   // survivor `lane`'s reduced triple
+        uint64_t mm = m;
+        for (uint32_t k = 0; mm && alive; ++k) {
+            const int s = __builtin_ctzll(mm);
+            mm &= mm - 1;
+            const uint64_t box = box_mask((uint32_t)__builtin_amdgcn_readlane((int)dsc, s));
+            const float4 q0 = wP4[k * 2 + 0], q1 = wP4[k * 2 + 1];
+            const float dx = fpx - q0.x, dy = fpy - q0.y;
+            const float md = gsr_blend_md2(dx, dy, q0.z, q0.w, q1.x, q1.y);
+            const float ee = gsr_blend_expf(-0.5f * md);
+            float alpha = q1.z * ee;
+            alpha = fminf(alpha, 0.99f);
+            const bool in = __builtin_amdgcn_inverse_ballot_w64(box);
+            const bool take = in & !(T < 1e-3f) & !(alpha < 1e-3f);
+            const uint64_t tb = __ballot(take);
+            if (tb) {   // uniform
+                // the weight of the take: k_blend_aux's alpha channel step with ca = 0
+                const float w = __builtin_fmaf(alpha, T, 0.0f);
+                if (STATS) {
+                    const bool mine = lane == s;
+                    // (without the count output: 1 = composited at all, for the guard below)
+                    const uint32_t pc = CNT ? (uint32_t)__builtin_popcountll(tb) : 1u;
+                    p_cnt = mine ? pc : p_cnt;
+                    if (WGT) {
+                        const uint32_t fx = take ? __float2uint_rn(w * 16777216.0f) : 0u;
+                        const uint32_t sum =
+                            (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(fx, OpAdd{}), 63);
+                        p_sum = mine ? sum : p_sum;
+                    }
+                    if (MAXW) {
+                        const uint32_t mx = wave_max_u32(take ? __float_as_uint(w) : 0u);
+                        p_max = mine ? mx : p_max;
+                    }
+                }
+                if (ID) {
+                    const int32_t g = __builtin_amdgcn_readlane((int)gidx, s);
+                    const bool better = take & (w > best_w);   // strictly: the first of equals stays
+                    best_w = better ? w : best_w;
+                    best_i = better ? g : best_i;
+                }
+                const float Tn = T * (1.0f - alpha);
+                T = take ? Tn : T;
+                alive = __ballot(!(T < 1e-3f)) != 0ull;
+            }
+        }
+        // ---- one atomic per statistic per survivor that some pixel composited (lane = survivor) ----
+        if (STATS && hit && p_cnt) {
+            if (CNT) atomicAdd(io.count + gidx, p_cnt);
+            if (WGT) atomicAdd(io.weight + gidx, (unsigned long long)p_sum);
+            if (MAXW) atomicMax(io.wmax + gidx, p_max);
+        }
+    }
+    if (ID && px < W && py < H) io.id[(size_t)py * (size_t)W + (size_t)px] = inside ? best_i : -1;
+}
+
 // ------------------------------------------------------------------ standalone sort ABI helpers
 
 // (u32(key) << 32 | i): the reference sorts int keys as unsigned 8-bit digits
@@ -4676,6 +4864,33 @@ hipError_t launch_blend_aux(const uint32_t* idx, const uint2* ranges, const uint
     if (nfeat == 0) go(std::integral_constant<int, 0>{});
     else if (nfeat <= 4) go(std::integral_constant<int, 4>{});
     else go(std::integral_constant<int, 8>{});
+    return hipGetLastError();
+}
+
+template <int WHAT>
+static void blend_contrib_go(int what, int ng, hipStream_t s, const uint32_t* idx, const uint2* ranges,
+                             const uint4* rec, const Frame& fr, int bands, const ContribIO& io) {
+    if constexpr (WHAT <= 15) {
+        if (what == WHAT)
+            hipLaunchKernelGGL((k_blend_contrib<WHAT>), dim3(ng), dim3(64), 0, s, idx, ranges, rec, fr.tiles_x,
+                               fr.tiles_y, fr.W, fr.H, fr.cover_w, fr.cover_h, bands, io);
+        else
+            blend_contrib_go<WHAT + 1>(what, ng, s, idx, ranges, rec, fr, bands, io);
+    }
+}
+
+hipError_t launch_blend_contrib(const uint32_t* idx, const uint2* ranges, const uint4* rec, const Frame& fr,
+                                uint32_t* count, unsigned long long* weight, uint32_t* wmax, int32_t* id,
+                                const uint32_t* overflow, int band_tiles, hipStream_t s) {
+    const int what = (count ? kContribCount : 0) | (weight ? kContribWeight : 0) | (wmax ? kContribMax : 0) |
+                     (id ? kContribId : 0);
+    if (!what || !overflow) return hipErrorInvalidValue;
+    const int nt = fr.tiles_x * fr.tiles_y;
+    if (nt <= 0) return hipSuccess;
+    int bands, ng;
+    blend_grid(nt, band_tiles, bands, ng);
+    const ContribIO io{count, weight, wmax, id, overflow};
+    blend_contrib_go<1>(what, ng, s, idx, ranges, rec, fr, bands, io);
     return hipGetLastError();
 }
 

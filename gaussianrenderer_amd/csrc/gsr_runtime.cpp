@@ -1545,6 +1545,18 @@ int ensure_aux_pack(gsr_context* c, int64_t n) {
     return GSR_OK;
 }
 
+// What follows an aux frame's blend: blend_locked's stage mark, timing and completion event.
+int blend_aux_done(gsr_context* c) {
+    mark(c, GSR_NUM_STAGES);
+    if (c->timing && c->timing_now) c->ev_frames.push_back(c->cur);
+    c->cur = FrameEvents{};
+    if (!c->pending && c->completion_events) {
+        HIP_TRY(hipEventRecord(c->done_ev, c->stream));
+        c->pending = true;
+    }
+    return GSR_OK;
+}
+
 // The sorted frame's blend with auxiliary targets: blend_locked's one-phase frame with
 // k_blend_aux in place of k_blend_w, and no diagnostics.
 int blend_aux_locked(gsr_context* c, float* d_out, const gsr_aux_targets& aux) {
@@ -1562,14 +1574,54 @@ int blend_aux_locked(gsr_context* c, float* d_out, const gsr_aux_targets& aux) {
     HIP_TRY(gsr::launch_blend_aux(pair_vals(c, c->pair_buf), c->ranges, c->rec, c->fr, d_out, aux.d_alpha,
                                   aux.d_depth, c->aux_z, aux.d_features, c->n, aux.nfeat, aux.d_feat_out, c->aux_pack,
                                   c->blend_band_tiles, c->stream));
-    mark(c, GSR_NUM_STAGES);
-    if (c->timing && c->timing_now) c->ev_frames.push_back(c->cur);
-    c->cur = FrameEvents{};
-    if (!c->pending && c->completion_events) {
-        HIP_TRY(hipEventRecord(c->done_ev, c->stream));
-        c->pending = true;
+    return blend_aux_done(c);
+}
+
+// The sorted frame's contribution statistics (gsr_render_contrib): k_blend_contrib in place
+// of k_blend_w, under GSR_STAGE_BLEND, no diagnostics.  The kernel reads the frame's
+// overflow word (stats[0], written by the binning / emission kernels queued before it).
+int blend_contrib_locked(gsr_context* c, const gsr_contrib_targets& out) {
+    mark(c, GSR_STAGE_BLEND);
+    HIP_TRY(gsr::launch_blend_contrib(pair_vals(c, c->pair_buf), c->ranges, c->rec, c->fr, out.d_count,
+                                      reinterpret_cast<unsigned long long*>(out.d_weight), out.d_max, out.d_id,
+                                      &c->stats[0].overflow, c->blend_band_tiles, c->stream));
+    return blend_aux_done(c);
+}
+
+// The frame policy of gsr_render_aux and gsr_render_contrib, around the frame's own blend.
+// One phase, exact blend, and the depth split's controller untouched: the preprocess
+// and the sort run with the split off (no threshold partition, no partial records, no
+// retry bookkeeping), and what the preprocess's overflow check learned from earlier
+// split frames is put back for the next non-aux frame's check to learn again (their
+// evidence is sticky) — unless that check reported an incomplete frame, whose
+// consequences (no more speculation) stand.
+template <typename Blend>
+int aux_frame_locked(gsr_context* c, const void* scene, int layout, int64_t n, const gsr_camera* cam, int W, int H,
+                     int nx, int ny, int ws, int hs, float k, void* stream, Blend&& blend) {
+    SplitCtl ctl;
+    split_ctl_save(c, &ctl);
+    const int state = split_state(c);
+    const int depth_split = c->depth_split;
+    c->depth_split = 0;
+    int rc = preprocess_locked(c, scene, layout, n, cam, W, H, nx, ny, ws, hs, k, stream);
+    int r2 = GSR_OK;
+    if (rc == GSR_OK || rc == GSR_E_OVERFLOW) {
+        r2 = sort_locked(c, false);
+        if (r2 == GSR_OK) r2 = blend();
+        c->split_state_hold = state;
     }
-    return GSR_OK;
+    c->depth_split = depth_split;
+    if (rc == GSR_E_OVERFLOW) {
+        // the view bookkeeping only
+        ctl.split_pm = c->split_pm;
+        ctl.split_floor = c->split_floor;
+        ctl.split_clean = c->split_clean;
+        ctl.split_spec = c->split_spec;
+        ctl.split_seen = c->split_seen;
+    }
+    split_ctl_restore(c, ctl);
+    if (rc != GSR_OK && rc != GSR_E_OVERFLOW) return rc;
+    return r2 ? r2 : rc;
 }
 
 }  // namespace
@@ -1586,36 +1638,20 @@ extern "C" int gsr_render_aux(gsr_context* c, const void* scene, int layout, int
     if (!d_out && !aux->d_alpha && !aux->d_depth && aux->nfeat == 0)
         return set_err(GSR_E_ARG, "gsr_render_aux: no output");
     std::lock_guard<std::mutex> lk(c->mu);
-    // One phase, exact blend, and the depth split's controller untouched: the preprocess
-    // and the sort run with the split off (no threshold partition, no partial records, no
-    // retry bookkeeping), and what the preprocess's overflow check learned from earlier
-    // split frames is put back for the next non-aux frame's check to learn again (their
-    // evidence is sticky) — unless that check reported an incomplete frame, whose
-    // consequences (no more speculation) stand.
-    SplitCtl ctl;
-    split_ctl_save(c, &ctl);
-    const int state = split_state(c);
-    const int depth_split = c->depth_split;
-    c->depth_split = 0;
-    int rc = preprocess_locked(c, scene, layout, n, cam, W, H, nx, ny, ws, hs, k, stream);
-    int r2 = GSR_OK;
-    if (rc == GSR_OK || rc == GSR_E_OVERFLOW) {
-        r2 = sort_locked(c, false);
-        if (r2 == GSR_OK) r2 = blend_aux_locked(c, d_out, *aux);
-        c->split_state_hold = state;
-    }
-    c->depth_split = depth_split;
-    if (rc == GSR_E_OVERFLOW) {
-        // the view bookkeeping only
-        ctl.split_pm = c->split_pm;
-        ctl.split_floor = c->split_floor;
-        ctl.split_clean = c->split_clean;
-        ctl.split_spec = c->split_spec;
-        ctl.split_seen = c->split_seen;
-    }
-    split_ctl_restore(c, ctl);
-    if (rc != GSR_OK && rc != GSR_E_OVERFLOW) return rc;
-    return r2 ? r2 : rc;
+    return aux_frame_locked(c, scene, layout, n, cam, W, H, nx, ny, ws, hs, k, stream,
+                            [&] { return blend_aux_locked(c, d_out, *aux); });
+}
+
+extern "C" int gsr_render_contrib(gsr_context* c, const void* scene, int layout, int64_t n, const gsr_camera* cam,
+                                  int W, int H, int nx, int ny, int ws, int hs, float k,
+                                  const gsr_contrib_targets* out, void* stream) {
+    if (!c) return set_err(GSR_E_ARG, "null context");
+    if (!out) return set_err(GSR_E_ARG, "gsr_render_contrib: null targets");
+    if (!out->d_count && !out->d_weight && !out->d_max && !out->d_id)
+        return set_err(GSR_E_ARG, "gsr_render_contrib: no output");
+    std::lock_guard<std::mutex> lk(c->mu);
+    return aux_frame_locked(c, scene, layout, n, cam, W, H, nx, ny, ws, hs, k, stream,
+                            [&] { return blend_contrib_locked(c, *out); });
 }
 
 // ------------------------------------------------------------------ frames in flight

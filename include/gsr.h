@@ -188,6 +188,55 @@ int gsr_render_aux(gsr_context* ctx, const void* d_scene, int layout, int64_t n,
                    int W, int H, int num_tile_x, int num_tile_y, int width_stride, int height_stride,
                    float k, float* d_out, const gsr_aux_targets* aux, void* stream);
 
+/* Contribution statistics: which Gaussians made gsr_render's image of this frame, and how
+ * much each contributed (picking, pruning and level of detail, visibility sets).  No image
+ * is written: this entry point runs its own blend kernel over the same tile lists.
+ *
+ * Pixel p composites splat i when it takes it under the exact blend's decisions (the
+ * reference's, render.cu:323-341: inside the splat's box, T >= 1e-3, alpha >= 1e-3).  The
+ * weight of that take is w_i(p) = fma(alpha, T, 0) — one rounding of alpha * T, alpha the
+ * clamped alpha and T the transmittance before the splat — so 0 < w <= 0.99, and the
+ * accumulated alpha of gsr_render_aux is the sum of a pixel's weights.
+ *
+ *   d_count[i]   += the number of pixels that composited Gaussian i
+ *   d_weight[i]  += the sum over those pixels of rint(w_i(p) * GSR_CONTRIB_WEIGHT_ONE)
+ *                   (round to nearest even; fixed point, 2^24 = 1.0)
+ *   d_max[i]      = max(d_max[i], float bits of the largest w_i(p)); the bits of positive
+ *                   floats order as unsigned integers, 0 = never composited
+ *   d_id[p]       = the composited Gaussian with the largest w_i(p): a later splat of the
+ *                   list replaces the held one only when its w is strictly greater; -1 where
+ *                   the pixel composited nothing or lies outside the covered area
+ *                   (W*H words, row 0 = bottom, as the image)
+ *
+ * The three per-Gaussian arrays (n words each) ACCUMULATE and are never cleared by the
+ * library: the caller zeroes them once, and every later frame (another camera, another
+ * time of a 4D scene) adds to them on `stream`, so a camera path yields multi-view totals.
+ * All three reductions are integer and independent of order: results are reproducible bit
+ * for bit.  d_id is OVERWRITTEN by every frame.  Every pointer may be NULL; a statistic
+ * that is not asked for is not computed.
+ *
+ * An incomplete frame adds nothing: a frame that overflows the pair buffer or the depth
+ * pass budget (reported through GSR_E_OVERFLOW or gsr_sync, as for gsr_render) leaves
+ * d_count, d_weight and d_max exactly as they were, and d_id unspecified; render it again.
+ *
+ * The frame policy is gsr_render_aux's: one phase with the exact blend whatever
+ * GSR_TUNE_BLEND_EXP says, the depth split off and its controller left exactly as it was;
+ * sorting, binning and the scene layouts (4D scenes render at gsr_set_time) are
+ * gsr_render's; the blend is timed under GSR_STAGE_BLEND; no diagnostics are written (the
+ * blend counters, the take map and the stamps keep the last non-aux frame's values).
+ * Stream-ordered, no allocation of its own.  Not offered through gsr_render_path.
+ * GSR_E_ARG, before any device work: every pointer NULL, or out NULL. */
+#define GSR_CONTRIB_WEIGHT_ONE 16777216u          /* 2^24: fixed-point scale of d_weight */
+typedef struct gsr_contrib_targets {
+    uint32_t* d_count;   /* n words, accumulated, or NULL */
+    uint64_t* d_weight;  /* n words, accumulated, or NULL */
+    uint32_t* d_max;     /* n words, accumulated (max of float bits), or NULL */
+    int32_t*  d_id;      /* W*H words, overwritten, or NULL */
+} gsr_contrib_targets;
+int gsr_render_contrib(gsr_context* ctx, const void* d_scene, int layout, int64_t n, const gsr_camera* cam,
+                       int W, int H, int num_tile_x, int num_tile_y, int width_stride, int height_stride,
+                       float k, const gsr_contrib_targets* out, void* stream);
+
 /* Offline camera path (config 4 on one GPU; the reference has no batch entry
  * point — it renders one frame per preprocessCUDAGaussians call, render.cu:871):
  * frame i renders cams[i] (at times[i] for 4D scenes; times may be NULL) into
