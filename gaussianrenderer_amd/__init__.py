@@ -30,7 +30,7 @@ __all__ = [
     "Camera", "GsrError", "Renderer", "Scene", "TilingInformation", "make_camera", "orbit",
     "loadGaussianCudaFromPly", "preprocessCUDAGaussians", "read_ply", "write_synthetic_ply",
     "SPLAT_DTYPE", "STAGES", "TILE_PX", "lib", "AUX_MAX_FEATURES", "DisplayTarget", "display_gl_current", "preprocessCUDAGaussiansGL",
-    "CONTRIB_WEIGHT_ONE", "ContribTargets",
+    "CONTRIB_WEIGHT_ONE", "ContribTargets", "mask_indices", "gather_planes",
 ]
 
 # gsr_read_splats record (include/gsr.h).
@@ -162,6 +162,36 @@ class Scene:
         check(lib().gsr_scene_download(self.ptr, soa.ctypes.data, self.n), "gsr_scene_download")
         return soa
 
+    def select(self, keep_ptr, indices_ptr=None, stream: int = 0) -> "Scene":
+        """A new owned scene of the Gaussians whose byte in the device mask keep_ptr (n uint8,
+        any non-zero value keeps) is set, in index order, built on the device
+        (gsr_scene_select, include/gsr.h); its .n is the kept count.  indices_ptr (optional,
+        room for n int32) receives the kept source indices, for gather_planes() on side
+        arrays.  Synchronous on `stream`."""
+        keep = _dev_ptr(keep_ptr)
+        if not keep and self.n > 0:
+            raise ValueError("Scene.select: keep_ptr is missing")
+        m = c_int64(-1)
+        ptr = lib().gsr_scene_select(self.ptr, self.narrays, self.n, keep or None, byref(m),
+                                     _dev_ptr(indices_ptr) or None, stream or None)
+        if not ptr:
+            raise GsrError(_native.GSR_E_ARG, "gsr_scene_select")
+        return Scene(ptr, int(m.value), narrays=self.narrays)
+
+    def gather(self, indices_ptr, m: int, bad_ptr=None, stream: int = 0) -> "Scene":
+        """A new owned scene of m Gaussians, Gaussian j being this scene's Gaussian
+        indices[j] (device int32, any order, repeats allowed), stream-ordered
+        (gsr_scene_gather).  An index outside [0, n) reads the nearest valid Gaussian and
+        counts into the device uint32 bad_ptr (optional; zero it first)."""
+        idx = _dev_ptr(indices_ptr)
+        if not idx and m > 0:
+            raise ValueError("Scene.gather: indices_ptr is missing")
+        ptr = lib().gsr_scene_gather(self.ptr, self.narrays, self.n, idx or None, int(m),
+                                     _dev_ptr(bad_ptr) or None, stream or None)
+        if not ptr:
+            raise GsrError(_native.GSR_E_ARG, "gsr_scene_gather")
+        return Scene(ptr, int(m), narrays=self.narrays)
+
     def free(self):
         if self.ptr and self.owned:
             lib().gsr_scene_free(self.ptr)
@@ -172,6 +202,43 @@ class Scene:
             self.free()
         except Exception:
             pass
+
+
+def _dev_ptr(p) -> int:
+    """A device address from an int or anything with .data_ptr() (a torch tensor); None -> 0."""
+    if p is None:
+        return 0
+    return int(p.data_ptr()) if hasattr(p, "data_ptr") else int(p)
+
+
+def mask_indices(keep_ptr, n: int, indices_ptr, stream: int = 0) -> int:
+    """Stable compaction of a device keep mask (gsr_mask_indices): writes the ascending indices
+    i < n whose mask byte is non-zero into the device int32 array indices_ptr (room for n;
+    words past the count are untouched) and returns their number.  Synchronous on `stream`."""
+    keep, idx = _dev_ptr(keep_ptr), _dev_ptr(indices_ptr)
+    if n > 0 and not keep:
+        raise ValueError("mask_indices: keep_ptr is missing")
+    if n > 0 and not idx:
+        raise ValueError("mask_indices: indices_ptr is missing")
+    m = c_int64(-1)
+    check(lib().gsr_mask_indices(keep or None, int(n), idx or None, byref(m), stream or None), "gsr_mask_indices")
+    return int(m.value)
+
+
+def gather_planes(dst_ptr, dst_stride: int, src_ptr, src_stride: int, nplanes: int, elem_bytes: int, n: int,
+                  indices_ptr, m: int, bad_ptr=None, stream: int = 0) -> None:
+    """dst[p*dst_stride + j] = src[p*src_stride + indices[j]] for p < nplanes, j < m, on the
+    device, stream-ordered (gsr_gather_planes): elements of 4 or 8 bytes copied as bits,
+    strides in elements.  An index outside [0, n) reads the nearest valid element and counts
+    into the device uint32 bad_ptr (optional; zero it first)."""
+    dst, src, idx = _dev_ptr(dst_ptr), _dev_ptr(src_ptr), _dev_ptr(indices_ptr)
+    if not idx:
+        raise ValueError("gather_planes: indices_ptr is missing")
+    if not (dst and src):
+        raise ValueError("gather_planes: dst_ptr / src_ptr is missing")
+    check(lib().gsr_gather_planes(dst, int(dst_stride), src, int(src_stride), int(nplanes), int(elem_bytes),
+                                  int(n), idx, int(m), _dev_ptr(bad_ptr) or None, stream or None),
+          "gsr_gather_planes")
 
 
 def loadGaussianCudaFromPly(path: str):

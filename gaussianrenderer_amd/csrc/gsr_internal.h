@@ -1,5 +1,5 @@
 // gsr_internal.h — shared between the host runtime (gsr_runtime.cpp) and the
-// gfx950 kernels (gsr_kernels.hip, gsr_probes.hip).  Not part of the public ABI.
+// gfx950 kernels (gsr_kernels.hip, gsr_scene_ops.hip, gsr_probes.hip).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -262,6 +262,19 @@ hipError_t launch_items_from_lwg(const gsr_lwg* rec, const uint64_t* src_perm, u
                                  uint32_t mask, uint64_t* items, hipStream_t s);
 hipError_t launch_gather_lwg(const gsr_lwg* in, const uint64_t* stage1, const uint64_t* stage2, uint32_t n,
                              gsr_lwg* out, hipStream_t s);
+
+// Scene editing (gsr_scene_ops.hip).  launch_mask_indices: indices[0 .. m) = the ascending i
+// < n with keep[i] != 0 (three launches); counts: mask_chunks(n) + 1 words of scratch, the last
+// of which receives m.  launch_gather_planes: dst[p * dst_stride + j] = src[p * src_stride +
+// idx[j]] for p < nplanes, j < m, elements of 4 or 8 bytes; an index outside [0, n) reads the
+// nearest valid element and counts into *bad (nullable).  scene_header (nullable): 256 bytes
+// that receive a gsr_scene_header {count m, stride dst_stride, narrays nplanes}, written by
+// the kernel (launched even for m == 0 when it is given).
+uint32_t mask_chunks(uint32_t n);
+hipError_t launch_mask_indices(const uint8_t* keep, uint32_t n, uint32_t* counts, int32_t* indices, hipStream_t s);
+hipError_t launch_gather_planes(void* dst, int64_t dst_stride, const void* src, int64_t src_stride, int nplanes,
+                                int elem_bytes, uint32_t n, const int32_t* idx, uint32_t m, uint32_t* bad,
+                                void* scene_header, hipStream_t s);
 
 // Device self-check of the lane order of same-address returning LDS atomics (the
 // RA rank path): runs k_rank_order_check synchronously on the current device and

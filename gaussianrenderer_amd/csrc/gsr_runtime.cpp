@@ -263,6 +263,128 @@ extern "C" int gsr_scene_copy(void* d_dst, const void* d_scene, int narrays, int
     return GSR_OK;
 }
 
+// ---- scene editing (kernels: gsr_scene_ops.hip) ----
+
+extern "C" int gsr_mask_indices(const uint8_t* d_keep, int64_t n, int32_t* d_indices, int64_t* m_out, void* stream) {
+    if (!m_out) return set_err(GSR_E_ARG, "gsr_mask_indices: null m_out");
+    if (n < 0 || n > INT32_MAX) return set_err(GSR_E_ARG, "gsr_mask_indices: n = %lld out of range", (long long)n);
+    if (n == 0) {
+        *m_out = 0;
+        return GSR_OK;
+    }
+    if (!d_keep || !d_indices) return set_err(GSR_E_ARG, "gsr_mask_indices: null pointer");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint32_t chunks = gsr::mask_chunks((uint32_t)n);
+    uint32_t* counts = nullptr;   // the chunk counts, then the total
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&counts), sizeof(uint32_t) * ((size_t)chunks + 1)));
+    uint32_t m = 0;
+    hipError_t e = gsr::launch_mask_indices(d_keep, (uint32_t)n, counts, d_indices, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&m, counts + chunks, sizeof m, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(counts);
+    if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_mask_indices failed: %s", hipGetErrorString(e));
+    *m_out = (int64_t)m;
+    return GSR_OK;
+}
+
+extern "C" int gsr_gather_planes(void* d_dst, int64_t dst_stride, const void* d_src, int64_t src_stride, int nplanes,
+                                 int elem_bytes, int64_t n, const int32_t* d_indices, int64_t m, uint32_t* d_bad,
+                                 void* stream) {
+    if (!d_dst || !d_src || !d_indices) return set_err(GSR_E_ARG, "gsr_gather_planes: null pointer");
+    if (elem_bytes != 4 && elem_bytes != 8)
+        return set_err(GSR_E_ARG, "gsr_gather_planes: elem_bytes = %d, not 4 or 8", elem_bytes);
+    if (nplanes < 1) return set_err(GSR_E_ARG, "gsr_gather_planes: nplanes = %d < 1", nplanes);
+    if (n < 0 || n > INT32_MAX || m < 0 || m > INT32_MAX || (m > 0 && n == 0))
+        return set_err(GSR_E_ARG, "gsr_gather_planes: n = %lld, m = %lld out of range", (long long)n, (long long)m);
+    if (src_stride < n || dst_stride < m)
+        return set_err(GSR_E_ARG, "gsr_gather_planes: stride smaller than its count (src %lld < %lld or dst %lld < %lld)",
+                       (long long)src_stride, (long long)n, (long long)dst_stride, (long long)m);
+    if (((uintptr_t)d_dst | (uintptr_t)d_src) % (uintptr_t)elem_bytes || (uintptr_t)d_indices % 4 ||
+        (d_bad && (uintptr_t)d_bad % 4))
+        return set_err(GSR_E_ARG, "gsr_gather_planes: misaligned pointer");
+    HIP_TRY(gsr::launch_gather_planes(d_dst, dst_stride, d_src, src_stride, nplanes, elem_bytes, (uint32_t)n,
+                                      d_indices, (uint32_t)m, d_bad, nullptr, static_cast<hipStream_t>(stream)));
+    return GSR_OK;
+}
+
+// The source block's header against (narrays, n), as gsr_scene_copy checks it, and its magic
+// (an AoS array is refused).  Synchronous 256-byte read.
+static int check_scene_block(const void* d_scene, int narrays, int64_t n, const char* who) {
+    gsr_scene_header h{};
+    hipError_t e = hipMemcpy(&h, d_scene, sizeof h, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return set_err(GSR_E_HIP, "%s: reading the header failed: %s", who, hipGetErrorString(e));
+    if (h.magic[0] != GSR_SCENE_MAGIC0 || h.magic[1] != GSR_SCENE_MAGIC1 || h.magic[2] != GSR_SCENE_MAGIC2 ||
+        h.magic[3] != GSR_SCENE_MAGIC3)
+        return set_err(GSR_E_ARG, "%s: not a scene block (an AoS array?)", who);
+    if (h.count != (uint64_t)n || h.narrays != (uint64_t)narrays || h.stride != (uint64_t)scene_stride(n))
+        return set_err(GSR_E_ARG, "%s: block holds %llu Gaussians x %llu arrays, not %lld x %d", who,
+                       (unsigned long long)h.count, (unsigned long long)h.narrays, (long long)n, narrays);
+    return GSR_OK;
+}
+
+// gsr_scene_gather after its argument and header checks.
+static void* scene_gather_checked(const void* d_scene, int narrays, int64_t n, const int32_t* d_indices, int64_t m,
+                                  uint32_t* d_bad, void* stream) {
+    const int64_t bytes = gsr_scene_bytes(narrays, m);
+    void* d = nullptr;
+    hipError_t e = hipMalloc(&d, (size_t)bytes);
+    if (e != hipSuccess) {
+        set_err(GSR_E_HIP, "hipMalloc(%lld) failed: %s", (long long)bytes, hipGetErrorString(e));
+        return nullptr;
+    }
+    e = gsr::launch_gather_planes(static_cast<char*>(d) + GSR_SCENE_HEADER_BYTES, scene_stride(m),
+                                  static_cast<const char*>(d_scene) + GSR_SCENE_HEADER_BYTES, scene_stride(n), narrays,
+                                  (int)sizeof(float), (uint32_t)n, d_indices, (uint32_t)m, d_bad, d,
+                                  static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) {
+        set_err(GSR_E_HIP, "gsr_scene_gather: launch failed: %s", hipGetErrorString(e));
+        (void)hipFree(d);
+        return nullptr;
+    }
+    return d;
+}
+
+extern "C" void* gsr_scene_gather(const void* d_scene, int narrays, int64_t n, const int32_t* d_indices, int64_t m,
+                                  uint32_t* d_bad, void* stream) {
+    if (m < 0 || m > INT32_MAX || (m > 0 && n == 0)) {
+        set_err(GSR_E_ARG, "gsr_scene_gather: m = %lld out of range (n = %lld)", (long long)m, (long long)n);
+        return nullptr;
+    }
+    if (gsr_scene_bytes(narrays, n) < 0) return nullptr;   // bad narrays or n: the message is set
+    if (!d_scene || (m > 0 && !d_indices)) {
+        set_err(GSR_E_ARG, "gsr_scene_gather: null pointer");
+        return nullptr;
+    }
+    if (check_scene_block(d_scene, narrays, n, "gsr_scene_gather") != GSR_OK) return nullptr;
+    return scene_gather_checked(d_scene, narrays, n, d_indices, m, d_bad, stream);
+}
+
+extern "C" void* gsr_scene_select(const void* d_scene, int narrays, int64_t n, const uint8_t* d_keep, int64_t* m_out,
+                                  int32_t* d_indices, void* stream) {
+    if (gsr_scene_bytes(narrays, n) < 0) return nullptr;   // bad narrays or n: the message is set
+    if (!d_scene || !m_out || (n > 0 && !d_keep)) {
+        set_err(GSR_E_ARG, "gsr_scene_select: null pointer");
+        return nullptr;
+    }
+    if (check_scene_block(d_scene, narrays, n, "gsr_scene_select") != GSR_OK) return nullptr;
+    int32_t* idx = d_indices;
+    if (!idx && n > 0) {
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&idx), sizeof(int32_t) * (size_t)n);
+        if (e != hipSuccess) {
+            set_err(GSR_E_HIP, "hipMalloc(%zu) failed: %s", sizeof(int32_t) * (size_t)n, hipGetErrorString(e));
+            return nullptr;
+        }
+    }
+    void* d = nullptr;
+    if (gsr_mask_indices(d_keep, n, idx, m_out, stream) == GSR_OK)
+        d = scene_gather_checked(d_scene, narrays, n, idx, *m_out, nullptr, stream);
+    if (idx != d_indices) {   // the private index list must outlive the gather that reads it
+        (void)hipStreamSynchronize(static_cast<hipStream_t>(stream));
+        (void)hipFree(idx);
+    }
+    return d;
+}
+
 extern "C" void* gsr_scene_upload(const float* host_soa, int64_t n) {
     return gsr_scene_upload_ex(host_soa, GSR_SCENE_NARRAYS, n);
 }

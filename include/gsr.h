@@ -553,6 +553,59 @@ int gsr_scene_copy(void* d_dst, const void* d_scene, int narrays, int64_t n, voi
 /* Copies every array of the block (38, 49 for 4D, 59 for SH-3) into host_soa. */
 int gsr_scene_download(const void* d_scene, float* host_soa, int64_t n);
 
+/* ---- scene editing: new scene blocks from a keep mask or an index list, on the device ----
+ *
+ * The consumer half of gsr_render_contrib: a scene block is immutable, and these calls build
+ * a new one (a pruned scene, a level-of-detail or visibility subset, a reordered scene)
+ * without the download / numpy / upload round trip, and cut the caller's per-Gaussian side
+ * arrays (gsr_render_aux's feature planes, gsr_render_contrib's accumulators) down in step.
+ * All four are context-free.  Indices are int32 (scene sizes are capped at INT32_MAX).
+ *
+ * A selection (a monotone index list) keeps index order, the depth sort's tie-break, so
+ * dropping Gaussians that no pixel composited (d_count == 0) leaves the exact blend's image
+ * bit for bit unchanged.
+ *
+ * Every argument error returns GSR_E_ARG (or NULL with the error set) before any device work:
+ * a null pointer, a bad narrays, negative n or m, n or m > INT32_MAX, elem_bytes not 4 or 8,
+ * nplanes < 1, a stride smaller than its count, m > 0 with n == 0. */
+
+/* Stable stream compaction: writes the ascending indices i < n with d_keep[i] != 0 (any
+ * non-zero byte keeps) into d_indices[0 .. m) and returns m in the HOST word *m_out.
+ * d_indices has room for n words; words at m and beyond are left untouched.  Enqueues on
+ * `stream`, then waits for it: SYNCHRONOUS, like the readbacks (it allocates and frees n / 1024
+ * bytes of scratch).  n == 0 gives m = 0 without device work. */
+int gsr_mask_indices(const uint8_t* d_keep, int64_t n, int32_t* d_indices, int64_t* m_out, void* stream);
+/* Planar gather: dst[p * dst_stride + j] = src[p * src_stride + d_indices[j]] for p < nplanes,
+ * j < m.  Elements are elem_bytes = 4 or 8 bytes, copied as bits; strides are in elements,
+ * src_stride >= n and dst_stride >= m; the buffers must not overlap.  Indices may come in any
+ * order and may repeat (m > n is legal).  Stream-ordered: no allocation, no wait.
+ * The kernel never forms an address from an unchecked index: an index outside [0, n) reads
+ * element min(max(index, 0), n - 1) instead, and *d_bad (may be NULL; a device word the caller
+ * zeroes) is incremented by the number of such indices.
+ * Cost: a monotone list reads every plane in near-coalesced runs and all stores are
+ * coalesced; a random permutation pays one cache line per element and plane, which is inherent
+ * to the SoA layout ("Scene editing"). */
+int gsr_gather_planes(void* d_dst, int64_t dst_stride, const void* d_src, int64_t src_stride, int nplanes,
+                      int elem_bytes, int64_t n, const int32_t* d_indices, int64_t m, uint32_t* d_bad,
+                      void* stream);
+/* A new scene block of m Gaussians (one hipMalloc; free with gsr_scene_free or hipFree):
+ * Gaussian j is Gaussian d_indices[j] of d_scene in all narrays arrays; count = m, stride = m
+ * rounded up to 64, the same narrays; elements in [m, stride) are unspecified, as after an
+ * upload.  d_scene's header is checked against (narrays, n) as gsr_scene_copy does (read
+ * synchronously); an AoS array or a mismatching block is refused.  The gather and the new
+ * header are written on `stream`: the block is valid for work queued on `stream` after the
+ * call.  Out-of-range indices and d_bad as in gsr_gather_planes.  m == 0 gives a header-only
+ * block.  Returns NULL and sets gsr_last_error on failure. */
+void* gsr_scene_gather(const void* d_scene, int narrays, int64_t n, const int32_t* d_indices, int64_t m,
+                       uint32_t* d_bad, void* stream);
+/* gsr_mask_indices followed by gsr_scene_gather: the scene of the Gaussians with d_keep[i] != 0,
+ * in index order; their number in the HOST word *m_out.  d_indices (may be NULL; room for n
+ * words): receives the kept source indices, for compacting side arrays with
+ * gsr_gather_planes.  SYNCHRONOUS on `stream` (m must be known before the block is
+ * allocated). */
+void* gsr_scene_select(const void* d_scene, int narrays, int64_t n, const uint8_t* d_keep, int64_t* m_out,
+                       int32_t* d_indices, void* stream);
+
 /* ---------------------------------------------------------------- host helpers */
 
 /* PLY reader with the semantics of loadGaussianCudaFromPly (misc.cu:13-134 +
