@@ -130,6 +130,20 @@ hipError_t launch_preprocess(const float* arrays, int64_t stride, int64_t n, con
                              uint4* rec, uint64_t* items, uint64_t* rect, bool packed, bool four_d, bool sh3,
                              float t, hipStream_t s, uint16_t* spans = nullptr,
                              const RecSplit* rs = nullptr);
+// The same for nc = 2..kPreMultiMax cameras of one 3D scene block in one launch
+// (k_preprocess_multi; gsr_render_path's frames in flight): each Gaussian is loaded once,
+// its view-independent part computed once, and camera c's results go to out[c] exactly as
+// launch_preprocess(fr[c], ...) writes them.  No 4D scenes, no RecSplit.
+constexpr int kPreMultiMax = 4;
+struct PreTargets {
+    uint4* rec;
+    uint64_t* items;
+    uint64_t* rect;
+    uint16_t* spans;   // nullable
+    bool packed;
+};
+hipError_t launch_preprocess_multi(const float* arrays, int64_t stride, int64_t n, int nc, const Frame* const* fr,
+                                   const PreTargets* out, bool sh3, hipStream_t s);
 // One stable LSD pass over u64 items on bits [shift, shift + bits) (bits <= 8).
 // n = n_dev ? *n_dev : n_host.  hist: 256 * groups u32, totals: 256 u32.
 // ranges (nullable, final tile-sort pass): per-tile {~start, end} of key (item >> 32),

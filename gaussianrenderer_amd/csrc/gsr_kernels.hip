@@ -151,8 +151,12 @@ __device__ __forceinline__ float md2_cutoff(float op) {
 // is S * M * M <= 4e7.
 __device__ __forceinline__ bool coef_ok(float v) { return v == 0.0f || fabsf(v) >= 0x1p-60f; }
 
-__device__ __forceinline__ uint4 cull_word(float a, float b, float c, float e, float op, float r, float g,
-                                           float bl) {
+// xs_op(): gsr_alpha_take_min_x(op), the word's only term that depends on the opacity alone
+// (k_preprocess_multi computes it once per Gaussian for all its cameras), evaluated where
+// the word needs it.
+template <class XsOp>
+__device__ __forceinline__ uint4 cull_word_xs(float a, float b, float c, float e, XsOp xs_op, float r, float g,
+                                              float bl) {
     const float inf = __builtin_huge_valf();
     const float h = 0.5f * (b + c);
     const bool pd = a > 0.0f && e > 0.0f && (a * e - h * h) > 1e-4f * (a * e);
@@ -166,8 +170,12 @@ __device__ __forceinline__ uint4 cull_word(float a, float b, float c, float e, f
     const float iv = pd ? -h * __builtin_amdgcn_rcpf(a) : 0.0f;
     // a conic that is not robustly PD never culls: xs = -inf makes block_cut +inf.  Its
     // alpha decisions come from the exact one-splat path (no fast proof), never xs.
-    const float xs = pd ? gsr_alpha_take_min_x(op) : -inf;
+    const float xs = pd ? xs_op() : -inf;
     return make_uint4(__float_as_uint(xs), __float_as_uint(ih), __float_as_uint(iv), __float_as_uint(fast ? S : inf));
+}
+__device__ __forceinline__ uint4 cull_word(float a, float b, float c, float e, float op, float r, float g,
+                                           float bl) {
+    return cull_word_xs(a, b, c, e, [&] { return gsr_alpha_take_min_x(op); }, r, g, bl);
 }
 
 // md2 cutoff of the block test from the record's xs: a lane with float md2 > -2 xs has
@@ -319,19 +327,23 @@ struct SoaWg {
     }
 };
 
+// preprocess_one in three parts, shared with k_preprocess_multi: the loads
+// (preprocess_load), the view-independent arithmetic (preprocess_cov3d and the opacity-only
+// terms, PreShared) and everything that depends on the camera (preprocess_camera).
 template <bool T4D, bool SH3>
-__device__ __forceinline__ uint32_t preprocess_one(const SoaWg& A,
-                                                   const Frame& fr, uint4* __restrict__ rec,
-                                                   uint64_t* __restrict__ items, uint64_t* __restrict__ rect,
-                                                   int packed, uint16_t* __restrict__ spans, float tnow,
-                                                   const RecSplit& rs, int64_t i) {
-    // depth split, key mode (RecSplit): 1 = records of the near Gaussians only, 2 = the
-    // far ones' records only (no item, rect or span writes: those are sorted already)
-    const bool far_pass = rs.mode == 2;
-    if (far_pass && rs.gate && *rs.gate == 0u) return 0xffffffffu;
-    const uint32_t kcut = rs.mode == 1 ? *rs.kcut : far_pass ? *rs.kcut_frame : 0xffffffffu;
-    // the frame's threshold, for the far record pass (the near sort copies it too)
-    if (rs.mode == 1 && i == 0) *rs.kcut_frame = kcut;
+struct PreLoads {
+    // Every load of the Gaussian but the late SH is issued before the cull decides
+    // whether it is needed: one memory round trip instead of three (position, then
+    // rotation / scale, then SH).  Wasted bytes for culled Gaussians only (config 2:
+    // 5 %).  The SH stays behind the cull in 4D (the temporal cull drops ~64 %) and
+    // SH-3 (48 coefficients) modes.
+    static constexpr bool kEarlySH = !T4D && !SH3;
+    float gx, gy, gz, tfac;
+    float q_in[4], s_in[3], op_in, sh_in[kEarlySH ? 27 : 1];
+};
+
+template <bool T4D, bool SH3>
+__device__ __forceinline__ void preprocess_load(const SoaWg& A, float tnow, PreLoads<T4D, SH3>& L) {
     float gx = A(GSR_A_X);
     float gy = A(GSR_A_Y);
     float gz = A(GSR_A_Z);
@@ -346,24 +358,74 @@ __device__ __forceinline__ uint32_t preprocess_one(const SoaWg& A,
         const float u = dt / A(GSR_A_TSCALE);
         tfac = gsr_expf(-(u * u));
     }
-    // Every other load of this Gaussian is issued here, before the cull decides
-    // whether it is needed: one memory round trip instead of three (position, then
-    // rotation / scale, then SH).  Wasted bytes for culled Gaussians only (config 2:
-    // 5 %).  The SH stays behind the cull in 4D (the temporal cull drops ~64 %) and
-    // SH-3 (48 coefficients) modes.
-    constexpr bool kEarlySH = !T4D && !SH3;
-    float q_in[4], s_in[3], op_in, sh_in[kEarlySH ? 27 : 1];
+    L.gx = gx; L.gy = gy; L.gz = gz; L.tfac = tfac;
 #pragma unroll
-    for (int k = 0; k < 4; k++) q_in[k] = A(GSR_A_ROT0 + k);
+    for (int k = 0; k < 4; k++) L.q_in[k] = A(GSR_A_ROT0 + k);
 #pragma unroll
-    for (int k = 0; k < 3; k++) s_in[k] = A(GSR_A_SCALE0 + k);
-    op_in = A(GSR_A_OPACITY);
-    if (kEarlySH) {
+    for (int k = 0; k < 3; k++) L.s_in[k] = A(GSR_A_SCALE0 + k);
+    L.op_in = A(GSR_A_OPACITY);
+    if (PreLoads<T4D, SH3>::kEarlySH) {
 #pragma unroll
-        for (int k = 0; k < 27; k++) sh_in[k] = A(GSR_A_SH0 + k);
+        for (int k = 0; k < 27; k++) L.sh_in[k] = A(GSR_A_SH0 + k);
     }
+}
+
+// World-space covariance R S S R^T of one Gaussian (render.cu:655-686, the part before
+// the camera rotation).
+__device__ __forceinline__ void preprocess_cov3d(const float* q_in, const float* s_in, float* cov) {
+    // buildRotMatFromQuat_cuda (math.cu:153-164)
+    float qw = q_in[0];
+    float qx = q_in[1];
+    float qy = q_in[2];
+    float qz = q_in[3];
+    const float qn = sqrtf(qx * qx + qy * qy + qz * qz + qw * qw);
+    qx /= qn; qy /= qn; qz /= qn; qw /= qn;
+    float Rm[9], RT[9], S[9], tmp[9];
+    Rm[0] = 1 - 2 * qy * qy - 2 * qz * qz; Rm[1] = 2 * qx * qy - 2 * qw * qz;     Rm[2] = 2 * qx * qz + 2 * qw * qy;
+    Rm[3] = 2 * qx * qy + 2 * qw * qz;     Rm[4] = 1 - 2 * qx * qx - 2 * qz * qz; Rm[5] = 2 * qy * qz - 2 * qw * qx;
+    Rm[6] = 2 * qx * qz - 2 * qw * qy;     Rm[7] = 2 * qy * qz + 2 * qw * qx;     Rm[8] = 1 - 2 * qx * qx - 2 * qy * qy;
+    RT[0] = Rm[0]; RT[1] = Rm[3]; RT[2] = Rm[6];
+    RT[3] = Rm[1]; RT[4] = Rm[4]; RT[5] = Rm[7];
+    RT[6] = Rm[2]; RT[7] = Rm[5]; RT[8] = Rm[8];
+    S[0] = s_in[0]; S[1] = 0.0f; S[2] = 0.0f;
+    S[3] = 0.0f; S[4] = s_in[1]; S[5] = 0.0f;
+    S[6] = 0.0f; S[7] = 0.0f; S[8] = s_in[2];
+    mm3(Rm, S, tmp);
+    mm3(tmp, S, Rm);
+    mm3(Rm, RT, cov);
+}
+
+// What k_preprocess_multi computes once per Gaussian for all its cameras (3D scenes: the
+// record's opacity is the scene's).
+struct PreShared {
+    float cov[9];   // preprocess_cov3d
+    float xs;       // gsr_alpha_take_min_x(op)
+    float cut;      // md2_cutoff(op)
+};
+
+// The camera-dependent part for Gaussian i against frame fr.  PRE: the view-independent
+// values come from *pre (else they are computed where they are first needed), and the SH-3
+// coefficients from sh3, loaded on the first camera that keeps the Gaussian (*have_sh3).
+// kcut and far_pass by reference, and the dead item through a named pointer: with these
+// k_preprocess<false, *> compile to the instructions they had as one function
+// (tools/kernel_isa_diff.py).
+template <bool T4D, bool SH3, bool PRE>
+__device__ __forceinline__ uint32_t preprocess_camera(const SoaWg& A, const PreLoads<T4D, SH3>& L,
+                                                      const PreShared* pre, float* sh3, bool* have_sh3,
+                                                      const Frame& fr, uint4* rec, uint64_t* items,
+                                                      uint64_t* rect, int packed, uint16_t* spans,
+                                                      const RecSplit& rs, const uint32_t& kcut, const bool& far_pass, int64_t i) {
+    constexpr bool kEarlySH = PreLoads<T4D, SH3>::kEarlySH;
+    const float gx = L.gx, gy = L.gy, gz = L.gz, tfac = L.tfac;
+    const float* q_in = L.q_in;
+    const float* s_in = L.s_in;
+    const float op_in = L.op_in;
+    const float* sh_in = L.sh_in;
     uint4* R = rec + 4 * i;
-    if (!far_pass) items[i] = ((uint64_t)0xffffffffu << 32) | (uint64_t)(uint32_t)i;
+    if (!far_pass) {
+        uint64_t* const dead = items + i;
+        *dead = ((uint64_t)0xffffffffu << 32) | (uint64_t)(uint32_t)i;
+    }
 
     // ---- view + clip transform and cull (render.cu:535-556) ----
     const float old_xyz[4] = {gx, gy, gz, 1.0f};
@@ -393,26 +455,13 @@ __device__ __forceinline__ uint32_t preprocess_one(const SoaWg& A,
     jacT[0] = jac[0]; jacT[1] = jac[3]; jacT[2] = jac[1];
     jacT[3] = jac[4]; jacT[4] = jac[2]; jacT[5] = jac[5];
 
-    // buildRotMatFromQuat_cuda (math.cu:153-164)
-    float qw = q_in[0];
-    float qx = q_in[1];
-    float qy = q_in[2];
-    float qz = q_in[3];
-    const float qn = sqrtf(qx * qx + qy * qy + qz * qz + qw * qw);
-    qx /= qn; qy /= qn; qz /= qn; qw /= qn;
-    float Rm[9], RT[9], S[9], tmp[9], cov[9];
-    Rm[0] = 1 - 2 * qy * qy - 2 * qz * qz; Rm[1] = 2 * qx * qy - 2 * qw * qz;     Rm[2] = 2 * qx * qz + 2 * qw * qy;
-    Rm[3] = 2 * qx * qy + 2 * qw * qz;     Rm[4] = 1 - 2 * qx * qx - 2 * qz * qz; Rm[5] = 2 * qy * qz - 2 * qw * qx;
-    Rm[6] = 2 * qx * qz - 2 * qw * qy;     Rm[7] = 2 * qy * qz + 2 * qw * qx;     Rm[8] = 1 - 2 * qx * qx - 2 * qy * qy;
-    RT[0] = Rm[0]; RT[1] = Rm[3]; RT[2] = Rm[6];
-    RT[3] = Rm[1]; RT[4] = Rm[4]; RT[5] = Rm[7];
-    RT[6] = Rm[2]; RT[7] = Rm[5]; RT[8] = Rm[8];
-    S[0] = s_in[0]; S[1] = 0.0f; S[2] = 0.0f;
-    S[3] = 0.0f; S[4] = s_in[1]; S[5] = 0.0f;
-    S[6] = 0.0f; S[7] = 0.0f; S[8] = s_in[2];
-    mm3(Rm, S, tmp);
-    mm3(tmp, S, Rm);
-    mm3(Rm, RT, cov);
+    float tmp[9], cov[9];
+    if (PRE) {
+#pragma unroll
+        for (int k = 0; k < 9; k++) cov[k] = pre->cov[k];
+    } else {
+        preprocess_cov3d(q_in, s_in, cov);
+    }
     mm3(fr.Rc, cov, tmp);
     mm3(tmp, fr.RcT, cov);
     gemm<2, 3, 3>(jac, cov, tmp);
@@ -510,6 +559,11 @@ __device__ __forceinline__ uint32_t preprocess_one(const SoaWg& A,
     const float C2_0 = 1.0925484305920792f, C2_1 = -1.0925484305920792f, C2_2 = 0.31539156525252005f,
                 C2_3 = -1.0925484305920792f, C2_4 = 0.5462742152960396f;
     float col[3];
+    if (PRE && SH3 && !*have_sh3) {
+#pragma unroll
+        for (int k = 0; k < 48; k++) sh3[k] = A(GSR_A_SH0 + k);
+        *have_sh3 = true;
+    }
     if (!SH3) {
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) {
@@ -534,7 +588,7 @@ __device__ __forceinline__ uint32_t preprocess_one(const SoaWg& A,
                     C3_6 = -0.5900435899266435f;
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) {
-            auto S = [&](int k) { return A(GSR_A_SH0 + ch + 3 * k); };   // coefficient k of channel ch
+            auto S = [&](int k) { return PRE ? sh3[ch + 3 * k] : A(GSR_A_SH0 + ch + 3 * k); };   // coefficient k of channel ch
             float r = kShC0 * S(0);
             r = r - kShC1 * y * S(1) + kShC1 * z * S(2) - kShC1 * x * S(3);
             r = r + C2_0 * xy * S(4) + C2_1 * yz * S(5) + C2_2 * (2.0f * zz - xx - yy) * S(6) +
@@ -555,17 +609,38 @@ __device__ __forceinline__ uint32_t preprocess_one(const SoaWg& A,
     // centre pixel stored as the float the blend computes with ((float)px, render.cu:329)
     R[2] = make_uint4(__float_as_uint((float)px_x), __float_as_uint((float)px_y), (uint32_t)xmin_px | ((uint32_t)xmax_px << 16),
                       (uint32_t)ymin_px | ((uint32_t)ymax_px << 16));
-    const uint4 cw = cull_word(ic0, ic1, ic2, ic3, opacity, col[0], col[1], col[2]);
+    const uint4 cw = PRE ? cull_word_xs(ic0, ic1, ic2, ic3, [&] { return pre->xs; }, col[0], col[1], col[2])
+                         : cull_word(ic0, ic1, ic2, ic3, opacity, col[0], col[1], col[2]);
     R[3] = cw;
     if (far_pass) return key;
     if (spans)
         spans[i] = tile_row_spans((float)px_x, (float)px_y, ic0, ic1, ic2, ic3,
                                   cw.x == __float_as_uint(-__builtin_huge_valf()) ? __builtin_huge_valf()
-                                                                                 : md2_cutoff(opacity),
+                                  : PRE                                           ? pre->cut
+                                                                                  : md2_cutoff(opacity),
                                   cw, xmin_px, xmax_px, ymin_px, ymax_px, tx0, tx1, ty0, ty1);
     put_rect(rect, i, trect, packed);
     items[i] = ((uint64_t)key << 32) | (uint64_t)(uint32_t)i;
     return key;
+}
+
+template <bool T4D, bool SH3>
+__device__ __forceinline__ uint32_t preprocess_one(const SoaWg& A,
+                                                   const Frame& fr, uint4* __restrict__ rec,
+                                                   uint64_t* __restrict__ items, uint64_t* __restrict__ rect,
+                                                   int packed, uint16_t* __restrict__ spans, float tnow,
+                                                   const RecSplit& rs, int64_t i) {
+    // depth split, key mode (RecSplit): 1 = records of the near Gaussians only, 2 = the
+    // far ones' records only (no item, rect or span writes: those are sorted already)
+    const bool far_pass = rs.mode == 2;
+    if (far_pass && rs.gate && *rs.gate == 0u) return 0xffffffffu;
+    const uint32_t kcut = rs.mode == 1 ? *rs.kcut : far_pass ? *rs.kcut_frame : 0xffffffffu;
+    // the frame's threshold, for the far record pass (the near sort copies it too)
+    if (rs.mode == 1 && i == 0) *rs.kcut_frame = kcut;
+    PreLoads<T4D, SH3> L;
+    preprocess_load<T4D, SH3>(A, tnow, L);
+    return preprocess_camera<T4D, SH3, false>(A, L, nullptr, nullptr, nullptr, fr, rec, items, rect, packed, spans,
+                                              rs, kcut, far_pass, i);
 }
 
 template <bool T4D, bool SH3>
@@ -580,6 +655,48 @@ __global__ __launch_bounds__(256) void k_preprocess(const float* __restrict__ ar
     if (i >= n) return;
     const SoaWg A{arr + i0, stride, 4u * threadIdx.x};
     (void)preprocess_one<T4D, SH3>(A, fr, rec, items, rect, packed, spans, tnow, rs, i);
+}
+
+// One Gaussian against the NC cameras of a camera path's frames in flight (3D scene blocks,
+// no depth split): the scene is read once and the view-independent part computed once, and
+// each camera's part runs as in k_preprocess into that camera's own outputs.
+struct PreOut {
+    uint4* rec;
+    uint64_t* items;
+    uint64_t* rect;
+    uint16_t* spans;   // nullable; used with packed rects only (as launch_preprocess)
+    int packed;
+};
+template <int NC>
+struct PreMulti {
+    Frame fr[NC];
+    PreOut out[NC];
+};
+
+template <bool SH3, int NC>
+__global__ __launch_bounds__(256) void k_preprocess_multi(const float* __restrict__ arr, int64_t stride, int64_t n,
+                                                          const PreMulti<NC> m) {
+    GSR_GEOM_PRIO();
+    const int64_t i0 = (int64_t)blockIdx.x * 256;
+    const int64_t i = i0 + threadIdx.x;
+    if (i >= n) return;
+    const SoaWg A{arr + i0, stride, 4u * threadIdx.x};
+    PreLoads<false, SH3> L;
+    preprocess_load<false, SH3>(A, 0.0f, L);
+    PreShared pre;
+    preprocess_cov3d(L.q_in, L.s_in, pre.cov);
+    pre.xs = gsr_alpha_take_min_x(L.op_in);
+    pre.cut = md2_cutoff(L.op_in);
+    float sh3[SH3 ? 48 : 1];
+    bool have_sh3 = false;
+    const RecSplit rs{0, nullptr, nullptr, nullptr};
+    const uint32_t kcut = 0xffffffffu;
+    const bool far_pass = false;
+#pragma unroll
+    for (int c = 0; c < NC; c++)
+        (void)preprocess_camera<false, SH3, true>(A, L, &pre, sh3, &have_sh3, m.fr[c], m.out[c].rec, m.out[c].items,
+                                                  m.out[c].rect, m.out[c].packed, m.out[c].spans, rs, kcut, far_pass,
+                                                  i);
 }
 
 // ------------------------------------------------------------------ radix sort
@@ -4487,6 +4604,30 @@ hipError_t launch_preprocess(const float* arrays, int64_t stride, int64_t n, con
     else
         hipLaunchKernelGGL((k_preprocess<false, false>), g, dim3(256), 0, s, arrays, stride, n, fr, rec, items, rect,
                            pk, packed ? spans : nullptr, t, rs);
+    return hipGetLastError();
+}
+
+hipError_t launch_preprocess_multi(const float* arrays, int64_t stride, int64_t n, int nc, const Frame* const* fr,
+                                   const PreTargets* out, bool sh3, hipStream_t s) {
+    if (nc < 2 || nc > kPreMultiMax) return hipErrorInvalidValue;
+    if (n <= 0) return hipSuccess;
+    const dim3 g(grid_for(n, 256));
+    auto go = [&](auto tag) {
+        constexpr int NC = decltype(tag)::value;
+        PreMulti<NC> m;
+        for (int c = 0; c < NC; c++) {
+            m.fr[c] = *fr[c];
+            m.out[c] = PreOut{out[c].rec, out[c].items, out[c].rect, out[c].packed ? out[c].spans : nullptr,
+                              out[c].packed ? 1 : 0};
+        }
+        if (sh3)
+            hipLaunchKernelGGL((k_preprocess_multi<true, NC>), g, dim3(256), 0, s, arrays, stride, n, m);
+        else
+            hipLaunchKernelGGL((k_preprocess_multi<false, NC>), g, dim3(256), 0, s, arrays, stride, n, m);
+    };
+    if (nc == 2) go(std::integral_constant<int, 2>{});
+    else if (nc == 3) go(std::integral_constant<int, 3>{});
+    else go(std::integral_constant<int, 4>{});
     return hipGetLastError();
 }
 

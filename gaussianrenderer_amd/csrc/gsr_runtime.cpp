@@ -609,6 +609,21 @@ struct gsr_context {
     int inflight = 3;
     std::vector<gsr_context*> lanes;          // lanes[l - 1] = child of lane l
     std::vector<hipStream_t> lane_streams;    // lane_streams[l - 1]
+    // shared preprocess (GSR_TUNE_PATH_SHARED_PRE): one k_preprocess_multi launch on lane 0's
+    // stream writes the preprocess outputs of every lane's frame of a group.  Each lane
+    // holds a second set of those outputs (alt_*, alt_cap Gaussians): the launch writes
+    // the set the lane's previous frames are not using, which becomes the lane's current
+    // set (switch_pre_set); alt_ev, on the lane's stream, marks the end of the work that
+    // used the other one.
+    int path_shared_pre = 1;
+    int64_t shared_launches = 0;     // GSR_TUNE_PATH_SHARED_LAUNCHES (lane 0 counts)
+    uint4* alt_rec = nullptr;
+    uint64_t* alt_items = nullptr;
+    uint64_t* alt_rect = nullptr;
+    uint16_t* alt_spans = nullptr;
+    int64_t alt_cap = 0;
+    hipEvent_t alt_ev = nullptr;
+    hipEvent_t pre_ev = nullptr;     // lane 0: after a group's shared launches
     hipEvent_t fork_ev = nullptr;
     std::vector<hipEvent_t> join_evs;         // one per child lane
     std::vector<hipEvent_t> alias_evs;        // ring of `inflight` events: output reuse across lanes
@@ -1015,6 +1030,10 @@ extern "C" void gsr_destroy(gsr_context* c) {
     for (auto e : c->join_evs) (void)hipEventDestroy(e);
     for (auto e : c->alias_evs) (void)hipEventDestroy(e);
     if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
+    if (c->alt_ev) (void)hipEventDestroy(c->alt_ev);
+    if (c->pre_ev) (void)hipEventDestroy(c->pre_ev);
+    for (auto* p : {(void*)c->alt_rec, (void*)c->alt_items, (void*)c->alt_rect, (void*)c->alt_spans})
+        if (p) (void)hipFree(p);
     for (auto* p : {(void*)c->rec, (void*)c->items[0], (void*)c->items[1], (void*)c->rect, (void*)c->pairs[0],
                     (void*)c->pairs[1], (void*)c->hist, (void*)c->totals, (void*)c->wg, (void*)c->stats, (void*)c->dstats,
                     (void*)c->ranges, (void*)c->soa_tmp, (void*)c->out_tmp, (void*)c->consumed, (void*)c->binmeta,
@@ -1039,8 +1058,11 @@ extern "C" int gsr_reserve(gsr_context* c, int64_t n, int64_t pairs) {
     return ensure_pairs(c, pairs);
 }
 
-static int preprocess_locked(gsr_context* c, const void* scene, int layout, int64_t n, const gsr_camera* cam,
-                             int W, int H, int nx, int ny, int ws, int hs, float k, void* stream) {
+// The host side of a frame's preprocess: the frame constants, the workspace, the split
+// controller and every per-frame decision (which sort follows, where the items go, packed
+// rects, spans, partial records).  Launches nothing but the AoS transpose.
+static int preprocess_plan(gsr_context* c, const void* scene, int layout, int64_t n, const gsr_camera* cam,
+                           int W, int H, int nx, int ny, int ws, int hs, float k, void* stream) {
     if (n < 0 || n > INT32_MAX) return set_err(GSR_E_ARG, "Gaussian count %lld out of range", (long long)n);
     if (n > 0 && !scene) return set_err(GSR_E_ARG, "null scene");
     if (layout != GSR_LAYOUT_SCENE_BLOCK && layout != GSR_LAYOUT_AOS && layout != GSR_LAYOUT_SCENE_BLOCK_4D &&
@@ -1147,19 +1169,36 @@ static int preprocess_locked(gsr_context* c, const void* scene, int layout, int6
     c->pre_scene = scene;
     c->pre_stride = stride;
     c->pre_layout = layout;
-    const gsr::RecSplit rsp{c->records_partial ? 1 : 0, c->kcut, c->kcut_frame, nullptr};
     if (c->split_key) {
         if (int rc = ensure_src(c, n)) return rc;
     }
     c->pre_out = c->split_key ? c->src_items : c->items[c->compact_frame || c->bds_frame ? 1 : 0];
-    HIP_TRY(gsr::launch_preprocess(arrays, stride, n, c->fr, c->rec, c->pre_out,
-                                   c->rect,
-                                   c->rect_packed, layout == GSR_LAYOUT_SCENE_BLOCK_4D,
-                                   layout == GSR_LAYOUT_SCENE_BLOCK_SH3, c->time, c->stream,
-                                   c->spans_frame ? c->spans : nullptr, &rsp));
+    return rc_over;
+}
+
+// The planned frame's preprocess is queued (by preprocess_launch or a shared launch).
+static void preprocess_queued(gsr_context* c) {
     c->have_pre = true;
     c->have_sort = false;
-    return rc_over;
+}
+
+static int preprocess_launch(gsr_context* c, hipStream_t s) {
+    const gsr::RecSplit rsp{c->records_partial ? 1 : 0, c->kcut, c->kcut_frame, nullptr};
+    HIP_TRY(gsr::launch_preprocess(c->pre_arrays, c->pre_stride, c->n, c->fr, c->rec, c->pre_out,
+                                   c->rect,
+                                   c->rect_packed, c->pre_layout == GSR_LAYOUT_SCENE_BLOCK_4D,
+                                   c->pre_layout == GSR_LAYOUT_SCENE_BLOCK_SH3, c->time, s,
+                                   c->spans_frame ? c->spans : nullptr, &rsp));
+    preprocess_queued(c);
+    return GSR_OK;
+}
+
+static int preprocess_locked(gsr_context* c, const void* scene, int layout, int64_t n, const gsr_camera* cam,
+                             int W, int H, int nx, int ny, int ws, int hs, float k, void* stream) {
+    const int rc = preprocess_plan(c, scene, layout, n, cam, W, H, nx, ny, ws, hs, k, stream);
+    if (rc != GSR_OK && rc != GSR_E_OVERFLOW) return rc;
+    if (int r2 = preprocess_launch(c, c->stream)) return r2;
+    return rc;
 }
 
 static void* pair_keys(gsr_context* c, int b) { return c->pairs[b]; }
@@ -1808,6 +1847,7 @@ void copy_settings(gsr_context* d, const gsr_context* s) {
 // Lanes 1..F-1: child contexts, streams and events, created once and kept.
 int ensure_lanes(gsr_context* c, int F) {
     if (!c->fork_ev) HIP_TRY(hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming));
+    if (!c->pre_ev) HIP_TRY(hipEventCreateWithFlags(&c->pre_ev, hipEventDisableTiming));
     while ((int)c->lanes.size() < F - 1) {
         gsr_context* l = new gsr_context();
         l->inflight = 1;
@@ -1832,6 +1872,30 @@ int ensure_lanes(gsr_context* c, int F) {
     }
     for (int l = 0; l < F - 1; l++) copy_settings(c->lanes[l], c);
     return GSR_OK;
+}
+
+// Shared preprocess: the lane's second set of preprocess outputs, as large as the first.
+int ensure_alt(gsr_context* c) {
+    if (!c->alt_ev) HIP_TRY(hipEventCreateWithFlags(&c->alt_ev, hipEventDisableTiming));
+    if (c->alt_cap >= c->n_cap) return GSR_OK;
+    HIP_TRY(hipDeviceSynchronize());
+    if (int rc = realloc_dev(&c->alt_rec, 4 * (size_t)c->n_cap)) return rc;
+    if (int rc = realloc_dev(&c->alt_items, (size_t)c->n_cap)) return rc;
+    if (int rc = realloc_dev(&c->alt_rect, (size_t)c->n_cap)) return rc;
+    if (int rc = realloc_dev(&c->alt_spans, (size_t)c->n_cap)) return rc;
+    c->alt_cap = c->n_cap;
+    return GSR_OK;
+}
+
+// The planned frame's preprocess outputs (records, the item buffer the plan chose, rects,
+// spans) become the other set; the set they were stays with whatever the lane has queued.
+void switch_pre_set(gsr_context* c) {
+    const int b = c->pre_out == c->items[1] ? 1 : 0;
+    std::swap(c->rec, c->alt_rec);
+    std::swap(c->items[b], c->alt_items);
+    std::swap(c->rect, c->alt_rect);
+    std::swap(c->spans, c->alt_spans);
+    c->pre_out = c->items[b];
 }
 
 int render_one_locked(gsr_context* c, const void* scene, int layout, int64_t n, const gsr_camera* cam, int W,
@@ -1931,51 +1995,167 @@ extern "C" int gsr_render_path_status(gsr_context* c, const void* scene, int lay
     auto hip_fail = [&](hipError_t e, const char* what) {
         return set_err(GSR_E_HIP, "gsr_render_path: %s: %s", what, hipGetErrorString(e));
     };
-    for (int i = 0; i < nframes && err == GSR_OK; i++) {
+    auto lane_ctx = [&](int lane) { return lane == 0 ? c : c->lanes[lane - 1]; };
+    auto lane_stream = [&](int lane) { return lane == 0 ? S : c->lane_streams[lane - 1]; };
+    // what frame i's lane waits for before it renders: the earlier writer of its output
+    // on another lane, and the caller's event
+    auto frame_waits = [&](int i) {
         const int lane = i % F;
-        gsr_context* lc = lane == 0 ? c : c->lanes[lane - 1];
-        const hipStream_t ls = lane == 0 ? S : c->lane_streams[lane - 1];
+        const hipStream_t ls = lane_stream(lane);
         if (prev[i] >= 0 && prev[i] % F != lane) {
-            if (hipError_t e = hipStreamWaitEvent(ls, c->alias_evs[prev[i] % F], 0)) {
-                err = hip_fail(e, "output reuse wait");
-                break;
-            }
+            if (hipError_t e = hipStreamWaitEvent(ls, c->alias_evs[prev[i] % F], 0))
+                return hip_fail(e, "output reuse wait");
         }
         if (wait_events && wait_events[i]) {
-            if (hipError_t e = hipStreamWaitEvent(ls, static_cast<hipEvent_t>(wait_events[i]), 0)) {
-                err = hip_fail(e, "wait event");
+            if (hipError_t e = hipStreamWaitEvent(ls, static_cast<hipEvent_t>(wait_events[i]), 0))
+                return hip_fail(e, "wait event");
+        }
+        return (int)GSR_OK;
+    };
+    // the frame's validity word is the lane's only while its frame is queued: the guard
+    // clears it on every exit, so a later gsr_render on this context (or an erroring
+    // frame's early return) never writes through a pointer the caller may have freed
+    struct StatusScope {
+        gsr_context* lc;
+        ~StatusScope() { lc->fstatus = nullptr; }
+    };
+    // rc: the frame's own result.  Notes an overflow, records the frame's events; returns an error
+    auto frame_done = [&](int i, int rc) {
+        const int lane = i % F;
+        const hipStream_t ls = lane_stream(lane);
+        if (rc == GSR_E_OVERFLOW) result = GSR_E_OVERFLOW;
+        else if (rc != GSR_OK) return rc;
+        if (record[i]) {
+            if (hipError_t e = hipEventRecord(c->alias_evs[lane], ls)) return hip_fail(e, "output reuse event");
+        }
+        if (frame_events && frame_events[i]) {
+            if (hipError_t e = hipEventRecord(static_cast<hipEvent_t>(frame_events[i]), ls))
+                return hip_fail(e, "frame event");
+        }
+        return (int)GSR_OK;
+    };
+    auto fail_hook = [&](int i) {   // GSR_TUNE_FAIL_FRAME (test hook, once)
+        if (!(c->fail_frame > 0 && i == c->fail_frame)) return (int)GSR_OK;
+        c->fail_frame = 0;
+        return set_err(GSR_E_ARG, "gsr_render_path: frame %d failed (GSR_TUNE_FAIL_FRAME test hook)", i);
+    };
+    // Shared preprocess (GSR_TUNE_PATH_SHARED_PRE): the frames of a group (one per lane) are
+    // planned first, then k_preprocess_multi launches on lane 0's stream write every lane's
+    // preprocess outputs (at most kPreMultiMax cameras per launch, a remainder of one by
+    // k_preprocess), and each lane sorts and blends on its own stream as usual.
+    const bool shared_ok = c->path_shared_pre && F >= 2 && n > 0 &&
+                           (layout == GSR_LAYOUT_SCENE_BLOCK || layout == GSR_LAYOUT_SCENE_BLOCK_SH3) &&
+                           !c->diagnostics && c->timing != 2;
+    for (int g0 = 0; g0 < nframes && err == GSR_OK; g0 += F) {
+        const int m = std::min(F, nframes - g0);
+        // the depth split off on every lane of the group (a lane's controller may turn it
+        // back on between groups; a plan that does so still writes the plain outputs)
+        bool shared = shared_ok && m >= 2;
+        for (int l = 0; l < m && shared; l++) shared = !split_enabled(lane_ctx(l), n);
+        if (shared) {
+            // plan: host only.  A plan that fails launches nothing for its frame or any after it
+            int planned = 0;
+            for (; planned < m && err == GSR_OK; planned++) {
+                const int i = g0 + planned;
+                gsr_context* lc = lane_ctx(planned);
+                lc->time = times ? times[i] : t_saved;
+                int rc = fail_hook(i);
+                if (rc == GSR_OK)
+                    rc = preprocess_plan(lc, scene, layout, n, &cams[i], W, H, nx, ny, ws, hs, k, lane_stream(planned));
+                if (rc == GSR_OK || rc == GSR_E_OVERFLOW) {
+                    if (rc == GSR_E_OVERFLOW) result = GSR_E_OVERFLOW;
+                    rc = ensure_alt(lc);
+                }
+                if (rc != GSR_OK) {
+                    err = rc;
+                    break;
+                }
+            }
+            int perr = GSR_OK;   // an error of the launches: none of the group's frames is rendered
+            auto hip_step = [&](hipError_t e, const char* what) {
+                if (e != hipSuccess && perr == GSR_OK) perr = hip_fail(e, what);
+            };
+            if (planned >= 2) {
+                // the launches overwrite each lane's other set: they wait for the work that
+                // used it (everything the lane had queued when it last switched sets), and for
+                // the events the caller gave the frames.  Then each lane marks the end of the
+                // work on its current set and switches.
+                for (int j = 0; j < planned; j++) {
+                    hip_step(hipStreamWaitEvent(S, lane_ctx(j)->alt_ev, 0), "shared preprocess wait");
+                    if (j > 0 && wait_events && wait_events[g0 + j])
+                        hip_step(hipStreamWaitEvent(S, static_cast<hipEvent_t>(wait_events[g0 + j]), 0), "wait event");
+                }
+                if (perr == GSR_OK) perr = frame_waits(g0);
+                for (int j = 0; j < planned && perr == GSR_OK; j++) {
+                    hip_step(hipEventRecord(lane_ctx(j)->alt_ev, lane_stream(j)), "shared preprocess event");
+                    if (perr == GSR_OK) switch_pre_set(lane_ctx(j));
+                }
+                for (int j = 0; j < planned && perr == GSR_OK;) {
+                    const int nc = std::min(gsr::kPreMultiMax, planned - j);
+                    if (nc == 1) {
+                        if (int rc = preprocess_launch(lane_ctx(j), S)) perr = rc;
+                    } else {
+                        const gsr::Frame* frs[gsr::kPreMultiMax];
+                        gsr::PreTargets outs[gsr::kPreMultiMax];
+                        for (int q = 0; q < nc; q++) {
+                            gsr_context* lc = lane_ctx(j + q);
+                            frs[q] = &lc->fr;
+                            outs[q] = gsr::PreTargets{lc->rec, lc->pre_out, lc->rect,
+                                                      lc->spans_frame ? lc->spans : nullptr, lc->rect_packed};
+                        }
+                        hip_step(gsr::launch_preprocess_multi(c->pre_arrays, c->pre_stride, n, nc, frs, outs,
+                                                              layout == GSR_LAYOUT_SCENE_BLOCK_SH3, S),
+                                 "shared preprocess");
+                        for (int q = 0; q < nc && perr == GSR_OK; q++) preprocess_queued(lane_ctx(j + q));
+                        if (perr == GSR_OK) c->shared_launches++;
+                    }
+                    j += nc;
+                }
+                if (perr == GSR_OK) hip_step(hipEventRecord(c->pre_ev, S), "shared preprocess event");
+                for (int j = 1; j < planned && perr == GSR_OK; j++)
+                    hip_step(hipStreamWaitEvent(lane_stream(j), c->pre_ev, 0), "shared preprocess wait");
+            } else if (planned == 1) {
+                perr = frame_waits(g0);
+                if (perr == GSR_OK) perr = preprocess_launch(c, S);
+            }
+            if (perr != GSR_OK) {
+                if (err == GSR_OK) err = perr;
                 break;
             }
+            // the frames planned before a failed plan still complete; an error of theirs is the earlier one
+            for (int j = 0; j < planned; j++) {
+                const int i = g0 + j;
+                gsr_context* lc = lane_ctx(j);
+                int rc = j > 0 ? frame_waits(i) : (int)GSR_OK;
+                if (rc == GSR_OK) {
+                    StatusScope status_scope{lc};
+                    lc->fstatus = d_status ? d_status[i] : nullptr;
+                    rc = sort_locked(lc, true);
+                    if (rc == GSR_OK) rc = blend_locked(lc, d_outs[i]);
+                    rc = frame_done(i, rc);
+                }
+                if (rc != GSR_OK) {
+                    err = rc;
+                    break;
+                }
+            }
+            continue;
         }
-        if (times) lc->time = times[i];
-        else lc->time = t_saved;
-        // the frame's validity word is the lane's only while its frame is queued: the guard
-        // clears it on every exit, so a later gsr_render on this context (or an erroring
-        // frame's early return) never writes through a pointer the caller may have freed
-        struct StatusScope {
-            gsr_context* lc;
-            ~StatusScope() { lc->fstatus = nullptr; }
-        } status_scope{lc};
-        lc->fstatus = d_status ? d_status[i] : nullptr;
-        int rc;
-        if (c->fail_frame > 0 && i == c->fail_frame) {   // GSR_TUNE_FAIL_FRAME (test hook, once)
-            c->fail_frame = 0;
-            rc = set_err(GSR_E_ARG, "gsr_render_path: frame %d failed (GSR_TUNE_FAIL_FRAME test hook)", i);
-        } else {
-            rc = render_one_locked(lc, scene, layout, n, &cams[i], W, H, nx, ny, ws, hs, k, d_outs[i], ls);
-        }
-        if (rc == GSR_E_OVERFLOW) {
-            result = GSR_E_OVERFLOW;
-        } else if (rc != GSR_OK) {
-            err = rc;
-            break;
-        }
-        if (record[i]) {
-            if (hipError_t e = hipEventRecord(c->alias_evs[lane], ls)) err = hip_fail(e, "output reuse event");
-        }
-        if (err == GSR_OK && frame_events && frame_events[i]) {
-            if (hipError_t e = hipEventRecord(static_cast<hipEvent_t>(frame_events[i]), ls))
-                err = hip_fail(e, "frame event");
+        for (int i = g0; i < g0 + m && err == GSR_OK; i++) {
+            const int lane = i % F;
+            gsr_context* lc = lane_ctx(lane);
+            if (int rc = frame_waits(i)) {
+                err = rc;
+                break;
+            }
+            lc->time = times ? times[i] : t_saved;
+            StatusScope status_scope{lc};
+            lc->fstatus = d_status ? d_status[i] : nullptr;
+            int rc = fail_hook(i);
+            if (rc == GSR_OK)
+                rc = render_one_locked(lc, scene, layout, n, &cams[i], W, H, nx, ny, ws, hs, k, d_outs[i],
+                                       lane_stream(lane));
+            err = frame_done(i, rc);
         }
     }
     // on every exit after the fork, errors included (render.cu:914-923 reports a failed
@@ -2301,6 +2481,8 @@ extern "C" int gsr_get_tuning(gsr_context* c, int knob, int* value) {
     case GSR_TUNE_BUCKET_ROWS: *value = c->fuse_rows; break;
     case GSR_TUNE_COL_CHUNK: *value = c->col_chunk; break;
     case GSR_TUNE_FAIL_FRAME: *value = c->fail_frame; break;
+    case GSR_TUNE_PATH_SHARED_PRE: *value = c->path_shared_pre; break;
+    case GSR_TUNE_PATH_SHARED_LAUNCHES: *value = (int)std::min<int64_t>(c->shared_launches, INT32_MAX); break;
     case GSR_TUNE_DEPTH_BUCKETS_OVER:
     case GSR_TUNE_DEPTH_BUCKETS_WORK: {
         auto get = [&](const gsr_context* x) -> int64_t {
@@ -2424,11 +2606,16 @@ extern "C" int gsr_set_tuning(gsr_context* c, int knob, int value) {
         if (value < 0) return set_err(GSR_E_ARG, "gsr_set_tuning: fail frame must be >= 0");
         c->fail_frame = value;
         return GSR_OK;
+    case GSR_TUNE_PATH_SHARED_PRE:
+        if (value != 0 && value != 1) return set_err(GSR_E_ARG, "gsr_set_tuning: shared preprocess must be 0 or 1");
+        c->path_shared_pre = value;
+        return GSR_OK;
     case GSR_TUNE_RANK_ATOMIC_ACTIVE:
     case GSR_TUNE_DEPTH_SPLIT_UNSAT:
     case GSR_TUNE_DEPTH_SPLIT_STATE:
     case GSR_TUNE_DEPTH_BUCKETS_OVER:
     case GSR_TUNE_DEPTH_BUCKETS_WORK:
+    case GSR_TUNE_PATH_SHARED_LAUNCHES:
         return set_err(GSR_E_ARG, "gsr_set_tuning: knob %d is read-only", knob);
     case GSR_TUNE_TILE_SORT_GROUPS:
     case GSR_TUNE_DEPTH_SORT_GROUPS:

@@ -504,10 +504,20 @@ enum {
                                         frame v with GSR_E_ARG (once; 0 = off, the default).  The
                                         frames queued before it are still joined to the caller's
                                         stream */
-    GSR_TUNE_DEPTH_BUCKETS_WORK = 33 /* read-only: the global path's items times the 8-bit passes each
+    GSR_TUNE_DEPTH_BUCKETS_WORK = 33,/* read-only: the global path's items times the 8-bit passes each
                                         took (their bucket's key span; tied keys take none), summed
                                         over the lanes; sticky, read after gsr_sync.  A frame adding
                                         more than n/8 makes the next frame reseed the splitters */
+    GSR_TUNE_PATH_SHARED_PRE = 34,   /* gsr_render_path*: 1 (default) = the frames in flight of a group
+                                        (one per lane) share one preprocess launch that reads the scene
+                                        once for up to four cameras (3D scene blocks, with or without
+                                        SH-3, depth split off, no diagnostics, no per-stage timing;
+                                        anything else keeps one launch per frame); each lane then holds
+                                        a second set of preprocess outputs, ~82 B per Gaussian, from
+                                        the first shared group on.  The shared launch runs on the
+                                        caller's stream and waits for the wait_events of the group's
+                                        frames.  0 = one launch per frame.  Same records, same image */
+    GSR_TUNE_PATH_SHARED_LAUNCHES = 35 /* read-only: shared preprocess launches this context has issued */
 };
 int gsr_set_tuning(gsr_context* ctx, int knob, int value);
 /* Current value of a knob (what gsr_set_tuning last set, else the default). */
