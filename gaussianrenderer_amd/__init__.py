@@ -21,7 +21,7 @@ from ctypes import byref, c_float, c_int, c_int64, c_void_p
 import numpy as np
 
 from . import _native
-from ._native import (AUX_MAX_FEATURES, AuxTargets, CONTRIB_WEIGHT_ONE, Camera, ContribTargets, GsrError, LAYOUT_AOS, LAYOUT_SCENE_BLOCK, LAYOUT_SCENE_BLOCK_4D,
+from ._native import (AUX_MAX_FEATURES, AuxTargets, BackwardTargets, CONTRIB_WEIGHT_ONE, Camera, ContribTargets, GsrError, LAYOUT_AOS, LAYOUT_SCENE_BLOCK, LAYOUT_SCENE_BLOCK_4D,
                       LAYOUT_SCENE_BLOCK_SH3, NUM_STAGES, PLY_SH3, PLY_TYPED, SCENE4D_NARRAYS, SCENE_NARRAYS,
                       SCENE_SH3_NARRAYS,
                       SPLAT_RECORD_BYTES, STAGES, TILE_PX, check, lib)
@@ -30,7 +30,7 @@ __all__ = [
     "Camera", "GsrError", "Renderer", "Scene", "TilingInformation", "make_camera", "orbit",
     "loadGaussianCudaFromPly", "preprocessCUDAGaussians", "read_ply", "write_synthetic_ply",
     "SPLAT_DTYPE", "STAGES", "TILE_PX", "lib", "AUX_MAX_FEATURES", "DisplayTarget", "display_gl_current", "preprocessCUDAGaussiansGL",
-    "CONTRIB_WEIGHT_ONE", "ContribTargets", "mask_indices", "gather_planes",
+    "CONTRIB_WEIGHT_ONE", "ContribTargets", "BackwardTargets", "mask_indices", "gather_planes",
 ]
 
 # gsr_read_splats record (include/gsr.h).
@@ -426,6 +426,38 @@ class Renderer:
                                       t.width_stride, t.height_stride, k, byref(out), stream or None)
         if rc not in (_native.GSR_OK, _native.GSR_E_OVERFLOW):
             raise GsrError(rc, "gsr_render_contrib")
+        return rc
+
+    def render_backward(self, scene, cam: Camera, W: int, H: int, grad_image_ptr=None, grad_alpha_ptr=None,
+                        color_ptr=None, opacity_ptr=None, conic_ptr=None, center_ptr=None, k: float = 3.0,
+                        tiling=None, stream: int = 0, layout: int = LAYOUT_SCENE_BLOCK, n: int | None = None,
+                        time: float | None = None) -> int:
+        """Enqueue one frame of the blend's backward pass (gsr_render_backward, include/gsr.h);
+        every pointer an int, anything with .data_ptr(), or None.  Inputs, at least one:
+        grad_image_ptr 3*W*H float32 (dL/d image) and grad_alpha_ptr W*H (dL/d accumulated alpha).
+        Outputs, at least one, float32, planar [c*n + i] and ACCUMULATED (zero them once; every
+        frame adds): color_ptr 3 planes, opacity_ptr 1, conic_ptr 4 (inv_covar[0..3]), center_ptr 2
+        (px_x, px_y): the gradients with respect to each Gaussian's splat record.  Summed with
+        float atomics: not reproducible in the last bits.  A frame that overflows adds nothing.
+        Same returns as render()."""
+        gi, ga = _dev_ptr(grad_image_ptr), _dev_ptr(grad_alpha_ptr)
+        outs = [_dev_ptr(p) for p in (color_ptr, opacity_ptr, conic_ptr, center_ptr)]
+        if not (gi or ga):
+            raise ValueError("render_backward: no upstream gradient given")
+        if not any(outs):
+            raise ValueError("render_backward: no output requested")
+        ptr = scene.ptr if isinstance(scene, Scene) else int(scene)
+        n = scene.n if n is None else n
+        if isinstance(scene, Scene) and layout == LAYOUT_SCENE_BLOCK:
+            layout = scene.layout
+        if time is not None:
+            self.set_time(time)
+        t = tiling or TilingInformation(1, 1, H, W)
+        bw = BackwardTargets(gi or None, ga or None, *[o or None for o in outs])
+        rc = lib().gsr_render_backward(self.ctx, ptr, layout, n, byref(cam), W, H, t.num_tile_x, t.num_tile_y,
+                                       t.width_stride, t.height_stride, k, byref(bw), stream or None)
+        if rc not in (_native.GSR_OK, _native.GSR_E_OVERFLOW):
+            raise GsrError(rc, "gsr_render_backward")
         return rc
 
     def set_frames_in_flight(self, frames: int):

@@ -115,6 +115,19 @@ class ContribTargets(ctypes.Structure):
     ]
 
 
+class BackwardTargets(ctypes.Structure):
+    """``gsr_backward_targets`` (include/gsr.h): the inputs and outputs of gsr_render_backward."""
+
+    _fields_ = [
+        ("d_grad_image", c_void_p),
+        ("d_grad_alpha", c_void_p),
+        ("d_color", c_void_p),
+        ("d_opacity", c_void_p),
+        ("d_conic", c_void_p),
+        ("d_center", c_void_p),
+    ]
+
+
 # (name, restype, argtypes) for every symbol of include/gsr.h and include/gsr_gl.h.
 SIGNATURES = [
     ("preprocessCUDAGaussians", None,
@@ -141,6 +154,8 @@ SIGNATURES = [
                                c_int, c_int, c_float, c_void_p, POINTER(AuxTargets), c_void_p]),
     ("gsr_render_contrib", c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(Camera), c_int, c_int, c_int, c_int,
                                    c_int, c_int, c_float, POINTER(ContribTargets), c_void_p]),
+    ("gsr_render_backward", c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(Camera), c_int, c_int, c_int, c_int,
+                                    c_int, c_int, c_float, POINTER(BackwardTargets), c_void_p]),
     ("gsr_render_path", c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(Camera), c_void_p, c_int, c_int,
                                 c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     ("gsr_render_path_ex", c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(Camera), c_void_p, c_int, c_int,

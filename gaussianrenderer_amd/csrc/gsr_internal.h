@@ -241,6 +241,15 @@ hipError_t launch_blend_aux(const uint32_t* idx, const uint2* ranges, const uint
 hipError_t launch_blend_contrib(const uint32_t* idx, const uint2* ranges, const uint4* rec, const Frame& fr,
                                 uint32_t* count, unsigned long long* weight, uint32_t* wmax, int32_t* id,
                                 const uint32_t* overflow, int band_tiles, hipStream_t s);
+// Backward pass of the exact blend (gsr_render_backward; k_blend_backward): the same
+// decisions over the same lists with k_blend_contrib's schedule, swept twice.  g_image (3 W*H
+// planes) / g_alpha (W*H), at least one: the upstream gradients.  color (3 planes of n),
+// opacity (n), conic (4 planes of n), center (2 planes of n), nullable each: ACCUMULATED with
+// float atomics, one per component per wave and taken splat.  overflow: as above.
+hipError_t launch_blend_backward(const uint32_t* idx, const uint2* ranges, const uint4* rec, const Frame& fr,
+                                 const float* g_image, const float* g_alpha, float* color, float* opacity,
+                                 float* conic, float* center, int64_t n, const uint32_t* overflow, int band_tiles,
+                                 hipStream_t s);
 // Stable partition of the preprocess items: visible first, culled last (both in
 // index order), visible count into *n_live; culled tail to out only, with dead
 // rects in srect (gsr_kernels.hip "live partition").  counts: groups words.

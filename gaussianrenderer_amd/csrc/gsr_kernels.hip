@@ -4495,6 +4495,288 @@ __global__ __launch_bounds__(64, 8) void k_blend_contrib(const uint32_t* __restr
     if (ID && px < W && py < H) io.id[(size_t)py * (size_t)W + (size_t)px] = inside ? best_i : -1;
 }
 
+// The upstream gradients k_blend_backward reads (W*H planes, nullable each), the planar
+// per-Gaussian gradient arrays it adds to (element [c * n + i], nullable each) and the
+// frame's overflow word.
+struct BackwardIO {
+    const float* g_image;
+    const float* g_alpha;
+    float* color;
+    float* opacity;
+    float* conic;
+    float* center;
+    int64_t n;
+    const uint32_t* overflow;
+};
+
+constexpr int kBackColor = 1, kBackOpacity = 2, kBackConic = 4, kBackCenter = 8;
+
+// Sums of NV per-lane values over the wave, jointly: v_permlane32_swap folds two values into
+// one register (lanes 0-31 then hold the first's sum over lane ^ 32, lanes 32-63 the
+// second's), v_permlane16_swap folds two of those (even rows of 16 lanes the first, odd rows
+// the second), and four row_ror adds finish inside the rows.  Afterwards every lane of row r
+// holds in x[i] the wave's total of value backward_slot(i, r) (an odd tail is paired with
+// itself, so some rows repeat a value): about NV / 2 + NV / 4 + NV adds (20 for nine values)
+// against the 6 NV of separate scans.
+template <int NV>
+__device__ __forceinline__ void wave_sum_packed(const float (&v)[NV], float (&x)[(NV + 3) / 4]) {
+    constexpr int NW = (NV + 1) / 2, NX = (NW + 1) / 2;
+    float w[NW];
+#pragma unroll
+    for (int i = 0; i < NW; i++) {
+        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[2 * i]),
+                                                        __float_as_uint(v[min(2 * i + 1, NV - 1)]), false, false);
+        w[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    }
+#pragma unroll
+    for (int i = 0; i < NX; i++) {
+        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(w[2 * i]),
+                                                        __float_as_uint(w[min(2 * i + 1, NW - 1)]), false, false);
+        float s = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+        s += __uint_as_float(dpp_u32<0x121, 0xf, true>(__float_as_uint(s)));   // row_ror:1
+        s += __uint_as_float(dpp_u32<0x122, 0xf, true>(__float_as_uint(s)));   // row_ror:2
+        s += __uint_as_float(dpp_u32<0x124, 0xf, true>(__float_as_uint(s)));   // row_ror:4
+        s += __uint_as_float(dpp_u32<0x128, 0xf, true>(__float_as_uint(s)));   // row_ror:8
+        x[i] = s;
+    }
+}
+// Which of the NV values row r holds in x[i] after wave_sum_packed, or -1 for a repeat.
+template <int NV>
+__device__ __forceinline__ int backward_slot(int i, int r) {
+    constexpr int NW = (NV + 1) / 2;
+    const int wi = 2 * i + (r & 1), vi = 2 * wi + (r >> 1);
+    return (wi < NW && vi < NV) ? vi : -1;
+}
+
+// The backward pass of the exact blend (gsr_render_backward): gradients of
+// L = sum over pixels of g_rgb . image + g_A alpha with respect to every composited splat's
+// record (colour, opacity, conic, centre), added to planar per-Gaussian arrays.
+// k_blend_contrib's schedule and decisions — one wave64 per 8x8 block, one-wave workgroups,
+// the same mapping, tile lists, 64-record batches, prefetch, conservative cull and survivor
+// compaction, the exact one-splat step, the early return on the overflow word.
+//
+// Forward order, two sweeps of the block's list in one kernel.  With u_j = g_rgb . colour_j
+// + g_A and P_j = sum_{k <= j} u_k alpha_k T_k, dL/dalpha_j = T_j u_j - (G - P_j) / (1 -
+// alpha_j), G = P_last: sweep 0 accumulates only P and leaves G, sweep 1 runs the same
+// instructions again (the sweep loop is not unrolled, so G - P_last is exactly 0) and forms
+// the gradients.  No division of T, no reversed lists.
+//
+// Per survivor that some lane takes, the wanted components (colour 3, opacity 1, conic 3 —
+// dL/db = dL/dc, one sum added to both planes — centre 2) are summed over the wave by
+// wave_sum_packed and written over the survivor's own LDS slot, which the loop has finished
+// reading; `taken` (a scalar mask) remembers which slots hold sums.  After the batch's loop
+// each such survivor's record lane reads its sums back and issues the float atomics: one per
+// component per (wave, taken splat), never one per pixel.  Their order of arrival is not
+// fixed, so the totals are not reproducible in the last bits.
+//
+// Survivor k's slot (12 dwords, read with wave-uniform addresses):
+//   [0] cx [1] cy [2] a [3] b | [4] c [5] e [6] opacity [7] r | [8] g [9] b [10..11] unused
+// WHAT: the kBack* bits of the outputs wanted; the others' sums drop out.
+template <int WHAT>
+__global__ __launch_bounds__(64, 8) void k_blend_backward(const uint32_t* __restrict__ idx,
+                                                          const uint2* __restrict__ ranges,
+                                                          const uint4* __restrict__ rec, int tiles_x, int tiles_y,
+                                                          int W, int H, int cover_w, int cover_h, int bands,
+                                                          BackwardIO io) {
+    constexpr bool COL = (WHAT & kBackColor) != 0, OPA = (WHAT & kBackOpacity) != 0;
+    constexpr bool CON = (WHAT & kBackConic) != 0, CEN = (WHAT & kBackCenter) != 0;
+    constexpr int oC = 0, oO = oC + (COL ? 3 : 0), oK = oO + (OPA ? 1 : 0), oX = oK + (CON ? 3 : 0);
+    constexpr int NV = oX + (CEN ? 2 : 0), NX = (NV + 3) / 4;
+    constexpr int kSlot = 12;
+    __shared__ float4 sP[64 * (kSlot / 4)];
+    if (*io.overflow) return;   // uniform: an incomplete frame adds nothing
+    const int ntiles = tiles_x * tiles_y;
+    const int vb = (int)blockIdx.x;
+    int L;
+    if (!blend_block_index(vb, ntiles, bands, L)) return;
+    const int tile = L >> 2, sub = L & 3;
+    const int tx = tile % tiles_x, ty = tile / tiles_x;
+    const int lane = (int)(threadIdx.x & 63u);
+    const uint2 rr = ranges[tile];                          // {~start, end}, zero = empty
+    const uint32_t beg = rr.y ? ~rr.x : 0u, end = rr.y;
+    const int bx = tx * GSR_TILE_PX + (sub & 1) * 8, by = ty * GSR_TILE_PX + (sub >> 1) * 8;
+    const float4* wP4 = sP;
+    float* wF = reinterpret_cast<float*>(sP);
+
+    const int px = bx + (lane & 7), py = by + (lane >> 3);
+    const bool inside = px < cover_w && py < cover_h;
+    const float fpx = (float)px, fpy = (float)py;
+    // the pixel's upstream gradient; pixels outside the covered area composite nothing
+    float g_r = 0.0f, g_g = 0.0f, g_b = 0.0f, g_a = 0.0f;
+    if (inside && px < W && py < H) {
+        const size_t o = (size_t)py * (size_t)W + (size_t)px;
+        const size_t hw = (size_t)W * (size_t)H;
+        if (io.g_image) {
+            g_r = io.g_image[o];
+            g_g = io.g_image[hw + o];
+            g_b = io.g_image[2 * hw + o];
+        }
+        if (io.g_alpha) g_a = io.g_alpha[o];
+    }
+
+    float G = 0.0f;
+#pragma nounroll
+    for (int sweep = 0; sweep < 2; ++sweep) {
+        // pixels outside the covered area start saturated and composite nothing (blend_block)
+        float T = inside ? 1.0f : 0.0f;
+        float P = 0.0f;
+        uint4 ra = make_uint4(0, 0, 0, 0), rb = ra, rc = ra, rd = ra;
+        uint32_t nidx = 0, cidx = 0;
+        if (beg + lane < end) {
+            cidx = idx[beg + lane];
+            const uint4* R = rec + 4 * (uint64_t)cidx;
+            ra = R[0];
+            rb = R[1];
+            rc = R[2];
+            rd = R[3];
+        }
+        if (beg + 64 + lane < end) nidx = idx[beg + 64 + lane];
+        bool alive = __ballot(!(T < 1e-3f)) != 0ull;
+        for (uint32_t base = beg; base < end && alive; base += 64) {
+            const uint32_t cnt = min(64u, end - base);
+            // ---- cull (lane = record): a copy of blend_block's, as are the load / prefetch around
+            // it (keep them identical): AABB vs block, the live-pixel filter, the ellipse-vs-block
+            // test ----
+            const uint64_t live_b = __ballot(!(T < 1e-3f));
+            bool hit;
+            uint32_t dsc;
+            {
+                const bool valid = (uint32_t)lane < cnt;
+                const int xmin = (int)(rc.z & 0xffffu), xmax = (int)(rc.z >> 16);
+                const int ymin = (int)(rc.w & 0xffffu), ymax = (int)(rc.w >> 16);
+                const bool box_hit = valid & !((xmax < bx) | (xmin > bx + 7) | (ymax < by) | (ymin > by + 7));
+                const float cx = __uint_as_float(rc.x), cy = __uint_as_float(rc.y);
+                const float a = __uint_as_float(ra.x), b = __uint_as_float(ra.y);
+                const float c = __uint_as_float(ra.z), e = __uint_as_float(ra.w);
+                const int x0 = max(xmin - bx, 0), x1 = min(xmax - bx, 7);
+                const int y0 = max(ymin - by, 0), y1 = min(ymax - by, 7);
+                const float dx0 = (float)(bx + x0) - cx, dx1 = (float)(bx + x1) - cx;
+                const float dy0 = (float)(by + y0) - cy, dy1 = (float)(by + y1) - cy;
+                // box descriptor (box_mask); shift counts masked to the hardware's: only lanes
+                // outside the box can have them out of range, and their results are discarded
+                const uint32_t colb = (0xffu >> ((uint32_t)(7 - (x1 - x0)) & 31u)) << ((uint32_t)x0 & 31u);
+                const uint32_t rsh = (uint32_t)(56 - 8 * (y1 - y0)) & 63u, lsh = (uint32_t)(8 * y0) & 63u;
+                dsc = colb | (rsh << 8) | (lsh << 16);
+                const uint64_t rows = (~0ull >> rsh) << lsh;
+                const uint32_t rep = __builtin_amdgcn_perm(colb, colb, 0u);   // colb in every byte
+                const uint64_t lrows = rows & live_b;
+                const float S = __uint_as_float(rd.w);
+                const float M = fmaxf(fmaxf(fabsf(dx0), fabsf(dx1)), fmaxf(fabsf(dy0), fabsf(dy1)));
+                const float SMM = S * M * M;
+                hit = box_hit & ((((uint32_t)lrows | (uint32_t)(lrows >> 32)) & rep) != 0u) &
+                      block_may_reach(a, b, c, e, __uint_as_float(rd.y), __uint_as_float(rd.z), dx0, dx1, dy0,
+                                      dy1, SMM, block_cut(__uint_as_float(rd.x)));
+            }
+            // ---- survivors, compacted in list order ----
+            const uint64_t m = __ballot(hit);
+            const uint32_t k_l =
+                __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            if (hit) {
+                float4* S4 = sP + k_l * (kSlot / 4);
+                S4[0] = make_float4(__uint_as_float(rc.x), __uint_as_float(rc.y), __uint_as_float(ra.x),
+                                    __uint_as_float(ra.y));
+                S4[1] = make_float4(__uint_as_float(ra.z), __uint_as_float(ra.w), __uint_as_float(rb.x),
+                                    __uint_as_float(rb.y));
+                S4[2] = make_float4(__uint_as_float(rb.z), __uint_as_float(rb.w), 0.0f, 0.0f);
+            }
+            const uint32_t gidx = cidx;   // this batch's Gaussian index of record `lane`
+            // ---- prefetch: records of batch k+1, indices of batch k+2 ----
+            if (base + 64 + lane < end) {
+                cidx = nidx;
+                const uint4* R = rec + 4 * (uint64_t)nidx;
+                ra = R[0];
+                rb = R[1];
+                rc = R[2];
+                rd = R[3];
+            }
+            if (base + 128 + lane < end) nidx = idx[base + 128 + lane];
+            // ---- the exact one-splat step over the survivors (render.cu:329-340) ----
+            uint64_t taken = 0;   // survivors whose slot holds sums
+            uint64_t mm = m;
+            for (uint32_t k = 0; mm && alive; ++k) {
+                const int s = __builtin_ctzll(mm);
+                mm &= mm - 1;
+                const uint64_t box = box_mask((uint32_t)__builtin_amdgcn_readlane((int)dsc, s));
+                const float4 q0 = wP4[k * 3 + 0], q1 = wP4[k * 3 + 1], q2 = wP4[k * 3 + 2];
+                const float dx = fpx - q0.x, dy = fpy - q0.y;
+                const float md = gsr_blend_md2(dx, dy, q0.z, q0.w, q1.x, q1.y);
+                const float ee = gsr_blend_expf(-0.5f * md);
+                const float oe = q1.z * ee;
+                const float alpha = fminf(oe, 0.99f);
+                const bool in = __builtin_amdgcn_inverse_ballot_w64(box);
+                const bool take = in & !(T < 1e-3f) & !(alpha < 1e-3f);
+                if (__ballot(take)) {   // uniform
+                    const float u = __builtin_fmaf(g_r, q1.w, __builtin_fmaf(g_g, q2.x, __builtin_fmaf(g_b, q2.y, g_a)));
+                    const float w = alpha * T;
+                    const float Pn = __builtin_fmaf(u, w, P);
+                    P = take ? Pn : P;
+                    if (sweep) {
+                        float v[NV];
+                        const float wt = take ? w : 0.0f;
+                        if (COL) {
+                            v[oC % NV] = g_r * wt;
+                            v[(oC + 1) % NV] = g_g * wt;
+                            v[(oC + 2) % NV] = g_b * wt;
+                        }
+                        if (OPA || CON || CEN) {
+                            // (1 - alpha >= 0.01; the clamped alpha passes nothing on)
+                            float da = T * u - (G - P) * __builtin_amdgcn_rcpf(1.0f - alpha);
+                            da = (take & !(oe > 0.99f)) ? da : 0.0f;
+                            if (OPA) v[oO % NV] = da * ee;
+                            const float dmd = -0.5f * oe * da;
+                            if (CON) {
+                                v[oK % NV] = dmd * dx * dx;
+                                v[(oK + 1) % NV] = dmd * dx * dy;
+                                v[(oK + 2) % NV] = dmd * dy * dy;
+                            }
+                            if (CEN) {
+                                const float bc = q0.w + q1.x;
+                                v[oX % NV] = -dmd * (2.0f * q0.z * dx + bc * dy);
+                                v[(oX + 1) % NV] = -dmd * (bc * dx + 2.0f * q1.y * dy);
+                            }
+                        }
+                        float x[NX];
+                        wave_sum_packed<NV>(v, x);
+                        if ((lane & 15) == 0) {
+#pragma unroll
+                            for (int i = 0; i < NX; i++) {
+                                const int vi = backward_slot<NV>(i, lane >> 4);
+                                if (vi >= 0) wF[k * kSlot + vi] = x[i];
+                            }
+                        }
+                        taken |= 1ull << k;
+                    }
+                    const float Tn = T * (1.0f - alpha);
+                    T = take ? Tn : T;
+                    alive = __ballot(!(T < 1e-3f)) != 0ull;
+                }
+            }
+            // ---- one atomic per component per survivor that some pixel composited (lane = survivor) ----
+            if (sweep && hit && ((taken >> k_l) & 1ull)) {
+                const float* r = wF + k_l * kSlot;
+                const int64_t n = io.n;
+                if (COL) {
+                    atomicAdd(io.color + gidx, r[oC]);
+                    atomicAdd(io.color + n + gidx, r[oC + 1]);
+                    atomicAdd(io.color + 2 * n + gidx, r[oC + 2]);
+                }
+                if (OPA) atomicAdd(io.opacity + gidx, r[oO]);
+                if (CON) {
+                    atomicAdd(io.conic + gidx, r[oK]);
+                    atomicAdd(io.conic + n + gidx, r[oK + 1]);
+                    atomicAdd(io.conic + 2 * n + gidx, r[oK + 1]);
+                    atomicAdd(io.conic + 3 * n + gidx, r[oK + 2]);
+                }
+                if (CEN) {
+                    atomicAdd(io.center + gidx, r[oX]);
+                    atomicAdd(io.center + n + gidx, r[oX + 1]);
+                }
+            }
+        }
+        G = P;
+    }
+}
+
 // ------------------------------------------------------------------ standalone sort ABI helpers
 
 // (u32(key) << 32 | i): the reference sorts int keys as unsigned 8-bit digits
@@ -5032,6 +5314,34 @@ hipError_t launch_blend_contrib(const uint32_t* idx, const uint2* ranges, const 
     blend_grid(nt, band_tiles, bands, ng);
     const ContribIO io{count, weight, wmax, id, overflow};
     blend_contrib_go<1>(what, ng, s, idx, ranges, rec, fr, bands, io);
+    return hipGetLastError();
+}
+
+template <int WHAT>
+static void blend_backward_go(int what, int ng, hipStream_t s, const uint32_t* idx, const uint2* ranges,
+                              const uint4* rec, const Frame& fr, int bands, const BackwardIO& io) {
+    if constexpr (WHAT <= 15) {
+        if (what == WHAT)
+            hipLaunchKernelGGL((k_blend_backward<WHAT>), dim3(ng), dim3(64), 0, s, idx, ranges, rec, fr.tiles_x,
+                               fr.tiles_y, fr.W, fr.H, fr.cover_w, fr.cover_h, bands, io);
+        else
+            blend_backward_go<WHAT + 1>(what, ng, s, idx, ranges, rec, fr, bands, io);
+    }
+}
+
+hipError_t launch_blend_backward(const uint32_t* idx, const uint2* ranges, const uint4* rec, const Frame& fr,
+                                 const float* g_image, const float* g_alpha, float* color, float* opacity,
+                                 float* conic, float* center, int64_t n, const uint32_t* overflow, int band_tiles,
+                                 hipStream_t s) {
+    const int what = (color ? kBackColor : 0) | (opacity ? kBackOpacity : 0) | (conic ? kBackConic : 0) |
+                     (center ? kBackCenter : 0);
+    if (!what || (!g_image && !g_alpha) || !overflow) return hipErrorInvalidValue;
+    const int nt = fr.tiles_x * fr.tiles_y;
+    if (nt <= 0 || n <= 0) return hipSuccess;
+    int bands, ng;
+    blend_grid(nt, band_tiles, bands, ng);
+    const BackwardIO io{g_image, g_alpha, color, opacity, conic, center, n, overflow};
+    blend_backward_go<1>(what, ng, s, idx, ranges, rec, fr, bands, io);
     return hipGetLastError();
 }
 

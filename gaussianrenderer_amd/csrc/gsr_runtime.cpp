@@ -1749,6 +1749,16 @@ int blend_contrib_locked(gsr_context* c, const gsr_contrib_targets& out) {
     return blend_aux_done(c);
 }
 
+// The sorted frame's backward pass (gsr_render_backward): k_blend_backward in place of
+// k_blend_w, under GSR_STAGE_BLEND, no diagnostics; the overflow word as above.
+int blend_backward_locked(gsr_context* c, const gsr_backward_targets& bw) {
+    mark(c, GSR_STAGE_BLEND);
+    HIP_TRY(gsr::launch_blend_backward(pair_vals(c, c->pair_buf), c->ranges, c->rec, c->fr, bw.d_grad_image,
+                                       bw.d_grad_alpha, bw.d_color, bw.d_opacity, bw.d_conic, bw.d_center, c->n,
+                                       &c->stats[0].overflow, c->blend_band_tiles, c->stream));
+    return blend_aux_done(c);
+}
+
 // The frame policy of gsr_render_aux and gsr_render_contrib, around the frame's own blend.
 // One phase, exact blend, and the depth split's controller untouched: the preprocess
 // and the sort run with the split off (no threshold partition, no partial records, no
@@ -1813,6 +1823,20 @@ extern "C" int gsr_render_contrib(gsr_context* c, const void* scene, int layout,
     std::lock_guard<std::mutex> lk(c->mu);
     return aux_frame_locked(c, scene, layout, n, cam, W, H, nx, ny, ws, hs, k, stream,
                             [&] { return blend_contrib_locked(c, *out); });
+}
+
+extern "C" int gsr_render_backward(gsr_context* c, const void* scene, int layout, int64_t n, const gsr_camera* cam,
+                                   int W, int H, int nx, int ny, int ws, int hs, float k,
+                                   const gsr_backward_targets* bw, void* stream) {
+    if (!c) return set_err(GSR_E_ARG, "null context");
+    if (!bw) return set_err(GSR_E_ARG, "gsr_render_backward: null targets");
+    if (!bw->d_grad_image && !bw->d_grad_alpha)
+        return set_err(GSR_E_ARG, "gsr_render_backward: no upstream gradient");
+    if (!bw->d_color && !bw->d_opacity && !bw->d_conic && !bw->d_center)
+        return set_err(GSR_E_ARG, "gsr_render_backward: no output");
+    std::lock_guard<std::mutex> lk(c->mu);
+    return aux_frame_locked(c, scene, layout, n, cam, W, H, nx, ny, ws, hs, k, stream,
+                            [&] { return blend_backward_locked(c, *bw); });
 }
 
 // ------------------------------------------------------------------ frames in flight

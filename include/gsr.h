@@ -237,6 +237,58 @@ int gsr_render_contrib(gsr_context* ctx, const void* d_scene, int layout, int64_
                        int W, int H, int num_tile_x, int num_tile_y, int width_stride, int height_stride,
                        float k, const gsr_contrib_targets* out, void* stream);
 
+/* Backward pass of the blend: how this frame's image and accumulated alpha react to each
+ * Gaussian's SPLAT RECORD — the colour, opacity, 2D conic (inv_covar[0..3] = a, b, c, e) and
+ * 2D centre (px_x, px_y) that the preprocess hands to the blend.  Carrying these on to the
+ * scene's position, scale, rotation and SH arrays (the projection's backward) is not part of
+ * this call.  No image is written: the call runs its own blend kernel over the tile lists.
+ *
+ * With upstream gradients g = (g_r, g_g, g_b) = d_grad_image and g_A = d_grad_alpha at every
+ * pixel (a NULL input counts as zeros), the function differentiated is
+ *   L = sum over pixels of g_rgb . image + g_A alpha
+ * of the exact blend.  For pixel p and the splats j = 1, 2, ... it takes (the reference's
+ * tests, render.cu:323-341: inside the box, T >= 1e-3, alpha >= 1e-3):
+ *   dx = p.x - cx, dy = p.y - cy, md2 = dx (a dx + b dy) + dy (c dx + e dy),
+ *   E = exp(-md2 / 2), alpha = min(o E, 0.99),
+ *   image += colour alpha T, alpha_acc += alpha T, T <- T (1 - alpha).
+ * The take decisions are piecewise constant and get no gradient.  With u_j = g_rgb .
+ * colour_j + g_A, P_j = sum_{k <= j} u_k alpha_k T_k and G = P_last:
+ *   d_color[ch]  += g_ch alpha_j T_j
+ *   dL/dalpha_j   = T_j u_j - (G - P_j) / (1 - alpha_j)
+ *   where o E > 0.99 the clamp is active and nothing reaches o or the geometry; otherwise
+ *   d_opacity    += dL/dalpha E,        dmd = -1/2 o E dL/dalpha,
+ *   d_conic      += dmd (dx^2, dx dy, dx dy, dy^2),
+ *   d_center     += -dmd (2 a dx + (b + c) dy, (b + c) dx + 2 e dy).
+ * The centre is differentiated as a real variable in the record's pixel coordinates, although
+ * the record itself holds whole pixels; mapping it further is the projection backward's
+ * business.  Pixels outside the covered area contribute nothing, whatever their g.
+ *
+ * The outputs are planar, element [c * n + i] for Gaussian i — the layout gsr_gather_planes
+ * cuts down after a prune.  Every output ACCUMULATES and is never cleared by the library, so
+ * a camera path sums a multi-view batch.  They are summed with float atomics whose order of
+ * arrival is not fixed: unlike every other output of this library, the results are NOT
+ * reproducible bit for bit; two runs can differ in the last bits.  An output that is not
+ * asked for is not computed.  A Gaussian no pixel composited is not touched at all.
+ *
+ * An incomplete frame (GSR_E_OVERFLOW here or from gsr_sync) adds nothing; render it again.
+ * The frame policy is gsr_render_contrib's: one phase with the exact blend whatever
+ * GSR_TUNE_BLEND_EXP says, the depth split off and its controller untouched, the blend timed
+ * under GSR_STAGE_BLEND, no diagnostics; sorting, binning and the scene layouts are
+ * gsr_render's.  Stream-ordered, no allocation of its own.  Not offered through
+ * gsr_render_path.  GSR_E_ARG, before any device work: bw NULL, both gradient inputs NULL,
+ * or every output NULL. */
+typedef struct gsr_backward_targets {
+    const float* d_grad_image;  /* 3*W*H, planar, row 0 = bottom: dL/d image; or NULL */
+    const float* d_grad_alpha;  /* W*H: dL/d (gsr_render_aux's accumulated alpha); or NULL */
+    float* d_color;    /* 3 planes of n floats: dL/d record colour     (ACCUMULATED), or NULL */
+    float* d_opacity;  /* n floats:             dL/d record opacity    (ACCUMULATED), or NULL */
+    float* d_conic;    /* 4 planes of n floats: dL/d inv_covar[0..3]   (ACCUMULATED), or NULL */
+    float* d_center;   /* 2 planes of n floats: dL/d (px_x, px_y)      (ACCUMULATED), or NULL */
+} gsr_backward_targets;
+int gsr_render_backward(gsr_context* ctx, const void* d_scene, int layout, int64_t n, const gsr_camera* cam,
+                        int W, int H, int num_tile_x, int num_tile_y, int width_stride, int height_stride,
+                        float k, const gsr_backward_targets* bw, void* stream);
+
 /* Offline camera path (config 4 on one GPU; the reference has no batch entry
  * point — it renders one frame per preprocessCUDAGaussians call, render.cu:871):
  * frame i renders cams[i] (at times[i] for 4D scenes; times may be NULL) into
