@@ -1,6 +1,8 @@
 // gsr_device.h — device helpers the gfx950 kernel translation units share (gsr_kernels.hip,
-// gsr_probes.hip): wave and workgroup scans, ballot ranking, chunk and XCD mappings, and the
-// host-side launch helpers.  Inline functions only: no kernels, no __constant__ data.
+// gsr_blend.hip, gsr_blend_derived.hip, gsr_scene_ops.hip, gsr_probes.hip): wave and workgroup
+// scans, ballot ranking, chunk and XCD mappings, the depth-sort pass plan, and the host-side
+// launch helpers.  Inline functions only: no kernels, no __constant__ data.  What only the
+// blend kernels share is in gsr_blend_device.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -189,11 +191,59 @@ __device__ __forceinline__ uint64_t match_peers(uint32_t d, bool valid, int bits
     return ((uint64_t)hi << 32) | lo;
 }
 
+// math.cu:131-138 (matVecMul4D_cuda).
+__device__ __forceinline__ void mv4(const float* M, const float* v, float* out) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        float acc = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc += M[i * 4 + j] * v[j];
+        out[i] = acc;
+    }
+}
+
+// Depth-sort pass plan.  dstats (zeroed per frame, filled by pass 0's upsweep
+// over every key except 0xFFFFFFFF, which culled records carry): [0] max of ~key
+// (= ~min key), [1] max key, [2] bit p set if some key has its low 8p bits all
+// ones, [3] nonzero if any such key exists.  Pass p >= 1 is an identity (and is
+// skipped) when every key shares the digits at and above p and no key has
+// all-ones low 8p bits: the 0xFFFFFFFF keys then already trail in index order,
+// exactly where the full sort puts them.  Skippable(p) implies skippable(p+1).
+__device__ __forceinline__ bool depth_pass_skipped(const uint32_t* __restrict__ dstats, int pass) {
+    if (!dstats || pass == 0) return false;
+    if (dstats[3] == 0u) return true;
+    const uint32_t kmin = ~dstats[0], kmax = dstats[1];
+    return (kmin >> (8 * pass)) == (kmax >> (8 * pass)) && !((dstats[2] >> pass) & 1u);
+}
+
+__device__ __forceinline__ int depth_passes_run(const uint32_t* __restrict__ dstats) {
+    int p = 1;
+    while (p < 4 && !depth_pass_skipped(dstats, p)) ++p;
+    return p;
+}
+
+// The depth sort ends in items[passes run & 1] (trailing identity passes are
+// skipped on the device).
+__device__ __forceinline__ const uint64_t* depth_sorted(const uint64_t* items0, const uint64_t* items1,
+                                                        const uint32_t* dstats) {
+    return (depth_passes_run(dstats) & 1) ? items1 : items0;
+}
+
 // f(std::true_type{}) or f(std::false_type{}): a runtime bool as a template argument of the
 // launches in the generic lambda f.
 template <typename F>
 inline auto with_bool(bool b, F&& f) {
     return b ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// f(std::integral_constant<int, v>{}) for a runtime v in [1, 15], nothing for any other v: a
+// runtime set of output bits as a template argument of the launch in the generic lambda f.
+template <int V = 1, typename F>
+inline void with_int_1_15(int v, F&& f) {
+    if constexpr (V <= 15) {
+        if (v == V) f(std::integral_constant<int, V>{});
+        else with_int_1_15<V + 1>(v, f);
+    }
 }
 
 inline int grid_for(int64_t n, int block) { return (int)((n + block - 1) / block); }

@@ -1,5 +1,6 @@
 // gsr_internal.h — shared between the host runtime (gsr_runtime.cpp) and the
-// gfx950 kernels (gsr_kernels.hip, gsr_scene_ops.hip, gsr_probes.hip).  Not part of the public ABI.
+// gfx950 kernels (gsr_kernels.hip, gsr_blend.hip, gsr_blend_derived.hip, gsr_scene_ops.hip,
+// gsr_probes.hip).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -96,7 +97,7 @@ struct RowSplit {
 };
 
 // The next frame's depth threshold (its partition puts keys < *kcut in the near part),
-// computed by phase A's blend from this frame's near depth order (gsr_kernels.hip
+// computed by phase A's blend from this frame's near depth order (gsr_blend.hip
 // split_cut_update).  kcut == nullptr: no update.
 struct SplitCut {
     const uint64_t* items0;
@@ -123,7 +124,8 @@ struct BlendSplit {
                                       // GSR_FRAME_SPEC_MISS into the frame's validity word (nullable)
 };
 
-// ---- launch wrappers (gsr_kernels.hip; the probes' in gsr_probes.hip) ----
+// ---- launch wrappers (gsr_kernels.hip; the blend's in gsr_blend.hip, its derived passes' in
+// gsr_blend_derived.hip, the probes' in gsr_probes.hip) ----
 hipError_t launch_aos_to_soa(const gsr_gaussian* aos, int64_t n, float* arrays, int64_t stride,
                              hipStream_t s);
 hipError_t launch_preprocess(const float* arrays, int64_t stride, int64_t n, const Frame& fr,
@@ -208,7 +210,7 @@ hipError_t launch_emit(const uint64_t* items0, const uint64_t* items1, const uin
 hipError_t launch_kv_pass(const void* keys_in, const uint32_t* vals_in, void* keys_out, uint32_t* vals_out,
                           bool key16, const uint32_t* n_dev, int shift, int bits, int groups, int items,
                           uint32_t* hist, uint32_t* totals, uint2* ranges, hipStream_t s);
-// One wave per 8x8 block (k_blend_w).  consumed: optional device counters
+// One wave per 8x8 block (k_blend_w, gsr_blend.hip).  consumed: optional device counters
 // (diagnostics: 16 counters, then a u64 take map entry per pixel), or with stamps the
 // per-wave timeline (tools/blend_timeline.py).  band_tiles > 0: bands of that many
 // tiles dealt round-robin to the XCDs; 0: one contiguous run of blocks per XCD.
@@ -218,7 +220,8 @@ hipError_t launch_kv_pass(const void* keys_in, const uint32_t* vals_in, void* ke
 hipError_t launch_blend(const uint32_t* idx, const uint2* ranges, const uint4* rec, const Frame& fr,
                         float* out, unsigned long long* consumed, bool stamps, int band_tiles, int blend_exp,
                         hipStream_t s, const BlendSplit* split = nullptr);
-// Auxiliary render targets (gsr_render_aux).  launch_aux_depth: z[i] = -Z of Gaussian i, the
+// Auxiliary render targets (gsr_render_aux; gsr_blend_derived.hip, like the contrib and
+// backward launches below).  launch_aux_depth: z[i] = -Z of Gaussian i, the
 // view-space z behind its depth key (n floats; arrays / stride / four_d / t as given to
 // launch_preprocess).  launch_blend_aux (k_blend_aux): the exact blend over the same lists
 // with k_blend_w's schedule, writing the colour planes (out, nullable), the accumulated
@@ -306,6 +309,7 @@ hipError_t rank_order_check(unsigned long long* lane_ops, unsigned long long* mi
 
 // Device math probe for the detmath GPU parity test.
 hipError_t launch_math_probe(const float* in, int n, float* out, hipStream_t s);
+// (gsr_blend.hip: the probe of the blend's own exp functions)
 hipError_t launch_exp_probe(uint32_t key_lo, uint32_t key_hi, float x_big, unsigned long long* viol, uint32_t* errs,
                             hipStream_t s);
 hipError_t launch_xs_probe(const float* op, int n, float* out, hipStream_t s);

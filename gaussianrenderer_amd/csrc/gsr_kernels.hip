@@ -1,5 +1,9 @@
-// gsr_kernels.hip — gfx950 (CDNA4) kernels of the 3DGS rasterizer (pipeline overview,
-// kernel by kernel: DESIGN.md section 9).
+// gsr_kernels.hip — gfx950 (CDNA4) kernels of the 3DGS rasterizer's geometry stages (pipeline
+// overview, kernel by kernel: DESIGN.md section 9).  Sections: AoS -> SoA, preprocess, blend
+// cull words (the per-record half of the blend's cull), radix sort, emission, tile binning,
+// bucket depth sort (with the depth split's k_split_sat), live partition, standalone sort
+// ABI helpers (and k_xs_probe), launchers.  The blend stage: gsr_blend.hip and
+// gsr_blend_derived.hip.
 //
 // Every float expression restates render.cu / math.cu in the same operation
 // order; the file is compiled with -ffp-contract=off so no FMA is formed
@@ -64,16 +68,7 @@ __device__ __forceinline__ void gemm(const float* A, const float* B, float* out)
         }
 }
 
-// math.cu:131-138 (matVecMul4D_cuda).
-__device__ __forceinline__ void mv4(const float* M, const float* v, float* out) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc += M[i * 4 + j] * v[j];
-        out[i] = acc;
-    }
-}
+// (matVecMul4D_cuda, mv4: gsr_device.h; k_aux_depth shares it)
 
 // Compact tile rectangle of one Gaussian for the emission: tx0 | tx1 << 16 |
 // ty0 << 32 | ty1 << 48; tile count (tx1 - tx0 + 1) * (ty1 - ty0 + 1), which
@@ -176,49 +171,6 @@ __device__ __forceinline__ uint4 cull_word_xs(float a, float b, float c, float e
 __device__ __forceinline__ uint4 cull_word(float a, float b, float c, float e, float op, float r, float g,
                                            float bl) {
     return cull_word_xs(a, b, c, e, [&] { return gsr_alpha_take_min_x(op); }, r, g, bl);
-}
-
-// md2 cutoff of the block test from the record's xs: a lane with float md2 > -2 xs has
-// -md2/2 < xs (exact scaling; the 1e-6 pad covers a subnormal -md2/2 rounding up to xs)
-// and fails the alpha test.  xs = -inf: +inf (never culls); +inf: -inf (always culls).
-__device__ __forceinline__ float block_cut(float xs) { return __builtin_fmaf(-2.0f, xs, 1e-6f); }
-
-// Can any pixel of an integer rectangle reach md2 <= cut?  dx0..dy1 bound the
-// (float)pixel - (float)centre offsets of the rectangle's pixels (monotone, so
-// every pixel's dx lies in [dx0, dx1]).  Returns false only when the exact
-// minimum of the quadratic form a dx^2 + (b+c) dx dy + e dy^2 over that
-// rectangle exceeds cut by more than a bound on the float rounding of md2
-// (<= ~6 ulp of |a|dx^2 + (|b|+|c|)|dx dy| + |e|dy^2, padded 10x) — so a culled
-// splat could never have composited onto this block.  cut, ih and iv come from
-// the record's cull word (cull_word), SMM = S M^2 with the word's S and M the largest
-// |offset| of the rectangle: a conic that is not robustly positive definite has
-// cut = +inf, a record without the per-record fast proof S = +inf (infinite margin);
-// NaN anywhere: never culled.
-__device__ __forceinline__ bool block_may_reach(float a, float b, float c, float e, float ih, float iv,
-                                                float dx0, float dx1, float dy0, float dy1, float SMM, float cut) {
-    // centre inside the rectangle: reachable.  Evaluated branch-free with the rest (the
-    // blend's cull runs it on every lane; a branch only adds exec-mask work)
-    const bool inside = (dx0 <= 0.0f) & (dx1 >= 0.0f) & (dy0 <= 0.0f) & (dy1 >= 0.0f);
-    // q = a x^2 + (b + c) x y + e y^2 in Horner form with explicit fused multiply-adds
-    // (5 VALU instead of 8): its rounding error stays a few ulp of the terms' magnitudes,
-    // far inside the margin below (4e-6 relative)
-    const float bc = b + c;
-    auto q = [&](float x, float y) { return __builtin_fmaf(x, __builtin_fmaf(a, x, bc * y), (e * y) * y); };
-    // The form is convex with its minimum at the splat centre (offset 0,0), which
-    // lies outside the rectangle here.  A far edge never holds the rectangle's
-    // minimum (from any of its points the segment toward the centre enters the
-    // interior, where the form is smaller), so only the near x-edge (when 0 is not
-    // in [dx0, dx1]) and the near y-edge (when 0 is not in [dy0, dy1]) are evaluated.
-    const float xe = dx0 > 0.0f ? dx0 : dx1, ye = dy0 > 0.0f ? dy0 : dy1;
-    // clamps as v_med3_f32: equal to fminf(fmaxf(v, lo), hi) here (lo <= hi; lo and hi
-    // both NaN or neither; quiet NaN v gives lo either way), without the two
-    // canonicalising v_max each fminf / fmaxf operand costs in IEEE mode
-    const float qx = q(xe, __builtin_amdgcn_fmed3f(ih * xe, dy0, dy1));
-    const float qy = q(__builtin_amdgcn_fmed3f(iv * ye, dx0, dx1), ye);
-    const bool x_out = dx0 > 0.0f || dx1 < 0.0f, y_out = dy0 > 0.0f || dy1 < 0.0f;
-    const float qm = fminf(x_out ? qx : 3.0e38f, y_out ? qy : 3.0e38f);
-    const float err = __builtin_fmaf(4e-6f, SMM, 1e-3f);   // SMM = S M M (S, M: see above)
-    return inside | !(qm - err > cut);
 }
 
 // Tile row spans (binning path, GSR_TUNE_TILE_SPANS).  A splat's tile rect is the
@@ -707,25 +659,8 @@ __global__ __launch_bounds__(256) void k_preprocess_multi(const float* __restric
 // wave64 ballot matching (the AMD stand-in for __match_any), scatters into LDS
 // in digit order and writes runs out coalesced.
 
-// Depth-sort pass plan.  dstats (zeroed per frame, filled by pass 0's upsweep
-// over every key except 0xFFFFFFFF, which culled records carry): [0] max of ~key
-// (= ~min key), [1] max key, [2] bit p set if some key has its low 8p bits all
-// ones, [3] nonzero if any such key exists.  Pass p >= 1 is an identity (and is
-// skipped) when every key shares the digits at and above p and no key has
-// all-ones low 8p bits: the 0xFFFFFFFF keys then already trail in index order,
-// exactly where the full sort puts them.  Skippable(p) implies skippable(p+1).
-__device__ __forceinline__ bool depth_pass_skipped(const uint32_t* __restrict__ dstats, int pass) {
-    if (!dstats || pass == 0) return false;
-    if (dstats[3] == 0u) return true;
-    const uint32_t kmin = ~dstats[0], kmax = dstats[1];
-    return (kmin >> (8 * pass)) == (kmax >> (8 * pass)) && !((dstats[2] >> pass) & 1u);
-}
-
-__device__ __forceinline__ int depth_passes_run(const uint32_t* __restrict__ dstats) {
-    int p = 1;
-    while (p < 4 && !depth_pass_skipped(dstats, p)) ++p;
-    return p;
-}
+// (the depth-sort pass plan — dstats, depth_pass_skipped, depth_passes_run, depth_sorted —
+// is in gsr_device.h: the blend's depth split reads the sorted order too)
 
 // SortRange (depth split, key mode; all fields null / 0 otherwise):
 //   base   the far part's positions [*base, n_host) are sorted on their own (n_dev unused)
@@ -1269,12 +1204,8 @@ __global__ __launch_bounds__(kSortThreads) void k_kv_downsweep(
 // written back in depth order (srect) so k_emit_pairs reads them coalesced.
 // Each thread issues all four of its index loads, then all four rect gathers,
 // so the dependent gathers overlap instead of running back to back.
-// The depth sort ends in items[passes run & 1] (trailing identity passes are
-// skipped on the device); the other buffer is free for srect.
-__device__ __forceinline__ const uint64_t* depth_sorted(const uint64_t* items0, const uint64_t* items1,
-                                                        const uint32_t* dstats) {
-    return (depth_passes_run(dstats) & 1) ? items1 : items0;
-}
+// The depth sort ends in items[passes run & 1] (depth_sorted); the other buffer is free
+// for srect.
 // The depth-ordered rect payloads the binning's depth sort carries (k_radix_downsweep):
 // same parity as the items.
 __device__ __forceinline__ const uint32_t* depth_sorted_rects(const uint32_t* pay0, const uint32_t* pay1,
@@ -2864,30 +2795,6 @@ __global__ __launch_bounds__(256) void k_bin_rows_count(uint32_t n, const uint32
     }
 }
 
-
-
-// Depth split: the next frame's threshold from this frame's near depth order: the key
-// at position na (the host's split point) when the near part holds more than na items,
-// else the threshold widened in proportion from the smallest key.  Any threshold gives
-// the same image.
-__device__ __forceinline__ void split_cut_update(const SplitCut& sc) {
-    const uint64_t* sorted = depth_sorted(sc.items0, sc.items1, sc.dstats);
-    const uint32_t m = sc.nnear ? min(*sc.nnear, sc.n) : sc.n;
-    uint32_t K;
-    if (sc.na < m) {
-        K = (uint32_t)(sorted[sc.na] >> 32);
-    } else {
-        const uint32_t k0 = *sc.kcut, kmin = m ? (uint32_t)(sorted[0] >> 32) : 0u;
-        if (m == 0 || k0 == 0xffffffffu || k0 <= kmin) {
-            K = 0xffffffffu;
-        } else {
-            const uint64_t span = (uint64_t)(k0 - kmin) * sc.na / m + 1u;
-            K = (uint32_t)min((uint64_t)kmin + span, (uint64_t)0xffffffffu);
-        }
-    }
-    *sc.kcut = K;
-}
-
 // Row pass, scan: one workgroup per row.  Exclusive scan of the row's item
 // counts over the workgroups (in place) and the row's totals.
 __global__ __launch_bounds__(256) void k_bin_rows_scan(uint32_t* __restrict__ hist, int groups, int tiles_y,
@@ -3393,1390 +3300,6 @@ __global__ __launch_bounds__(256) void k_part_scatter(const uint64_t* __restrict
     }
 }
 
-// ------------------------------------------------------------------ blend
-
-
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-// Packed product with the HIGH half of the second operand broadcast to both lanes,
-// in one v_pk_mul_f32 through op_sel (the compiler otherwise copies that half into
-// a fresh register pair first: one v_mov per use in the compositing loop).
-// Same IEEE products as the plain expressions (multiplication commutes exactly).
-__device__ __forceinline__ f2 pk_mul_b_hi(f2 a, f2 b) {   // (a.x * b.y, a.y * b.y)
-    f2 r;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// Packed fused multiply-adds with the second factor's LOW / HIGH half broadcast:
-// (fma(a.x, b.x, c.x), fma(a.y, b.x, c.y)) and (fma(a.x, b.y, c.x), fma(a.y, b.y, c.y)).
-__device__ __forceinline__ f2 pk_fma_b_lo(f2 a, f2 b, f2 c) {
-    f2 r;
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1]" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-__device__ __forceinline__ f2 pk_fma_b_hi(f2 a, f2 b, f2 c) {
-    f2 r;
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-
-// gsr_blend_expf on two lanes at once (v_pk_* for every float op that has a packed
-// form: 11 packed + 4 single VALU, against 11 + 6 for the Cephes gsr_expf), for
-// inputs the caller has PROVEN finite and in [-2e7, 5]: on [-104, 5] the clamp and
-// the NaN select do not change the result and every remaining step is the same IEEE
-// operation in the same order, so each half is bit-identical to gsr_blend_expf of
-// that half.  Below -104 (no clamp here) n <= -150 — for |x log2 e| >= 2^22 the
-// shifter no longer rounds to an integer and the remainder r drifts to |r| < 1.5,
-// still finite — so ldexp(y, n) rounds to +0, the clamped result
-// (gsr_exp_probe counts the halves that differ from the scalar function over every
-// float of [-2e7, 5]: none).  Out-of-box lanes are discarded by the caller.
-__device__ __forceinline__ f2 gsr_blend_expf_x2(f2 xc) {
-    const f2 t = __builtin_elementwise_fma(xc, (f2)1.44269504088896341f, (f2)12582912.0f);
-    const f2 n = t - 12582912.0f;
-    f2 r = __builtin_elementwise_fma(-n, (f2)0.693359375f, xc);
-    r = __builtin_elementwise_fma(-n, (f2)-2.12194440e-4f, r);
-    f2 q = __builtin_elementwise_fma((f2)0x1.6b42a4p-10f, r, (f2)0x1.125e6cp-7f);
-    q = __builtin_elementwise_fma(q, r, (f2)0x1.5557c2p-5f);
-    q = __builtin_elementwise_fma(q, r, (f2)0x1.555452p-3f);
-    q = __builtin_elementwise_fma(q, r, (f2)0x1.fffffcp-2f);
-    const f2 r2 = r * r;
-    const f2 y = __builtin_elementwise_fma(q, r2, r) + 1.0f;
-    f2 res;
-    res.x = __builtin_amdgcn_ldexpf(y.x, (int)n.x);
-    res.y = __builtin_amdgcn_ldexpf(y.y, (int)n.y);
-    return res;
-}
-
-// The blend's fast exp (GSR_TUNE_BLEND_EXP 1): e^x as the hardware 2^t (v_exp_f32) of
-// t = x log2(e), two lanes at once.  Its relative difference from gsr_blend_expf, with the
-// alpha product, is bounded on the argument range a composited lane can have
-// (kFxEpsMax, kFxEpsBig below; measured exhaustively by gsr_exp_probe); the
-// alpha decisions never use it (xs), and the transmittance test is guarded.
-__device__ __forceinline__ f2 fast_expf_x2(f2 x) {
-    const f2 t = x * 1.44269504088896341f;
-    f2 q;
-    q.x = __builtin_amdgcn_exp2f(t.x);
-    q.y = __builtin_amdgcn_exp2f(t.y);
-    return q;
-}
-
-// Fast-exp blend: bounds on |alpha_fast / alpha_exact - 1| for a composited lane
-// (opacity in [0, 1] and alpha_exact >= 1e-3, so the exp argument x lies in
-// [ln(1e-3), 5]; alpha > 0.5 needs x > ln 0.5, alpha > 0.9 needs x > ln 0.9).  Each is
-// the exhaustive maximum of |fast_expf / gsr_blend_expf - 1| over every float x of its
-// range (gsr_exp_probe; tests/test_gpu_fastexp.py checks these constants stay above
-// it) plus 2^-23 for the two roundings of op * e:
-//   kFxEps3  all composited lanes (x >= -6.95)
-//   kFxEps2  alpha > 0.5            (x >= -0.70)
-//   kFxEps1  alpha > 0.9            (x >= -0.11)
-// The transmittance of a pixel then differs from the exact chain's by a relative
-//   rho <= 207.1 kFxEps1 + 6.9078 max(3.909 kFxEps2, 1.4427 kFxEps3) + 3 2^-24 n
-// (n = composited splats, bounded by the wave's splat-iterations) up to and including
-// the step where it first drops below 1e-3 ("Fast exp"):
-// kFxBand0 and kFxBandStep are those terms with 2 % headroom.  The n term counts the
-// roundings per composite: the exact chain's two (1 - alpha, then the product) and the
-// fast chain's one (T - T alpha as one fma).
-constexpr float kFxEps3 = 6.6e-7f;
-constexpr float kFxEps2 = 4.8e-7f;
-constexpr float kFxEps1 = 4.8e-7f;
-constexpr float kFxBand0 = 1.02f * (207.1f * kFxEps1 + 6.9078f * (3.909f * kFxEps2 > 1.4427f * kFxEps3
-                                                                  ? 3.909f * kFxEps2 : 1.4427f * kFxEps3));
-constexpr float kFxBandStep = 1.02f * 3.0f * 0x1p-24f;
-
-// Set in the batch's last pair's second box descriptor (bit 30: above the survivor lane
-// at bits 24-29; box_mask reads bits 0-21 only).
-constexpr uint32_t kLastPair = 0x40000000u;
-
-// n + (lane's bit of ma) + (lane's bit of mb): the wave masks are the carry-ins of two
-// v_addc_co_u32 (one VALU each; counting booleans compiles to selects and an add).
-__device__ __forceinline__ uint32_t count_lanes2(uint32_t n, uint64_t ma, uint64_t mb) {
-    uint64_t c0, c1;
-    asm("v_addc_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(n), "=s"(c0) : "v"(n), "s"(ma));
-    asm("v_addc_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(n), "=s"(c1) : "v"(n), "s"(mb));
-    (void)c0;
-    (void)c1;
-    return n;
-}
-
-// The band for one pixel from what it composited so far: n splats, the largest alpha
-// m.  Besides the worst case above (band0 = kFxBand0), the alpha terms obey
-//   sum alpha_i / (1 - alpha_i) <= (sum alpha_i) / (1 - m)
-//                              <= (ln 1000 + ln(1 / (1 - m))) / (1 - m)
-// (alpha <= -ln(1 - alpha), and the exact T stayed >= 1e-3 before the step being
-// tested, whose own alpha is <= m), so rho <= kFxEps3 of that, which is far smaller
-// unless some alpha came near 0.99.  2 % headroom over the hardware log / rcp.
-// band0 < 0 (measurement builds only) turns the guard off.
-__device__ __forceinline__ float fx_band(float band0, uint32_t n, float m) {
-    const float om = 1.0f - m;                                 // >= 0.01 (alpha <= 0.99)
-    const float lnm = -0.693147181f * __builtin_amdgcn_logf(om);   // ln(1 / (1 - m))
-    const float byM = 1.02f * kFxEps3 * (6.9078f + lnm) * __builtin_amdgcn_rcpf(om);
-    return __builtin_fmaf((float)n, kFxBandStep, band0 < 0.0f || band0 > 0.5f ? band0 : fminf(band0, byM));
-}
-
-// One wave64 per 8x8 pixel block (four per 16x16 tile, one tile per
-// workgroup), no workgroup barrier.  Each wave streams its tile's splat list in
-// 64-record batches (records of batch k+1 and indices of batch k+2 prefetched
-// into registers).  Per batch, lane l culls record l (AABB, then the exact
-// ellipse-vs-block test) and computes its 64-bit in-AABB pixel mask; the
-// survivors are compacted, in list order, into PAIR SLOTS of the wave's LDS
-// slice so that {parameter of splat 2j, parameter of splat 2j+1} are adjacent
-// and feed v_pk_* instructions directly.  The compositing loop takes two
-// splats per iteration: md2, exp and alpha packed, then the two composites in
-// list order.  Batches holding a survivor without the fast-path proof run an
-// exact one-splat path instead (same values, full gsr_blend_expf, plain selects).
-//
-// Pair slot dwords (h = 0 / 1 for the first / second splat of the pair):
-//   [0+h] cx  [2+h] cy  [4+h] a  [6+h] b  [8+h] c  [10+h] e  [12+h] opacity
-//   [14+2h] red  [15+2h] green  [18+h] blue  (fast exp only: [20+h] xs)
-//   [22+h] box descriptor | survivor lane << 24 (0: no splat)
-struct BlendDiag {
-    uint64_t loaded = 0, iter = 0, active = 0, taken = 0, slow = 0, zero_taken = 0, no_cand_pairs = 0;
-};
-
-// 64-bit pixel mask (bit row * 8 + col) of a box descriptor built in the cull:
-// bits 0-7 the column byte, 8-15 = 56 - 8 (y1 - y0), 16-23 = 8 y0.  Uniform input,
-// so it compiles to scalar instructions.
-__device__ __forceinline__ uint64_t box_mask(uint32_t d) {
-    const uint32_t rep = (d & 0xffu) * 0x01010101u;
-    const uint64_t rows = (~0ull >> ((d >> 8) & 0xffu)) << ((d >> 16) & 0xffu);
-    return rows & (((uint64_t)rep << 32) | rep);
-}
-
-// Diagnostics take map: per pixel, the number of splats composited and a sum of
-// a mix of their Gaussian indices (the oracle's orc_render_takes computes the same).
-__device__ __forceinline__ uint32_t take_mix(uint32_t g) { return (g + 1u) * 2654435761u; }
-
-// The block L (tile-major index: tile << 2 | sub-block) of workgroup vb of k_blend_w and
-// k_blend_aux; false for a padding workgroup.  bands > 1: band j of B consecutive blocks goes
-// to XCD j mod 8; else one contiguous run of blocks per XCD (xcd_chunk).  (k_blend_w's comment.)
-__device__ __forceinline__ bool blend_block_index(int vb, int ntiles, int bands, int& L) {
-    if (bands > 1) {
-        const int nu = 4 * ntiles;
-        const int B = (nu + 8 * bands - 1) / (8 * bands);
-        const int k = vb >> 3;
-        L = ((k / B) * 8 + (vb & 7)) * B + k % B;
-        if (L >= nu) return false;
-    } else {
-        if (vb >= ntiles * 4) return false;
-        L = xcd_chunk(vb, ntiles * 4);
-    }
-    return true;
-}
-
-// One 8x8 pixel block (bx, by) blended by one wave over the tile list
-// idx[beg, end), using the wave's private LDS slice wP (32 pair slots).
-//
-// FX (fast exp, GSR_TUNE_BLEND_EXP 1): alpha from fast_expf_x2; the alpha test is
-// the exact one through the record's xs (-md2/2 >= xs, gsr_alpha_take_min_x), so
-// only the transmittance can differ from the exact chain, by less than the band
-// kFxBand0 + kFxBandStep n.  The wave flags a pixel ("suspect") when a value of T on
-// either side of its first drop below 1e-3 lies within the band of 1e-3, or when
-// it ends unsaturated within the band; then the exact T could have taken the other
-// branch.  The block writes every other pixel and returns the suspect mask; the
-// caller blends the suspect pixels again exactly (FX false, `only` = the mask).  A
-// batch holding a record without the fast proof aborts the fast pass (all ones, no
-// pixel written).  Every pixel therefore composites exactly the splats the exact
-// blend composites, in the same order.
-//
-// SPLIT (depth split, exact blend only): 1 = phase A, which composites the block's
-// phase-A list and, when some pixel is still unsaturated at its end, saves every
-// pixel's T in tsave (64 floats), sets *flag and counts the block in *gate (else
-// clears *flag); 2 = phase B, which resumes such a block from the saved T and the
-// colours phase A wrote (and, with DIAG, the take map).  Each pixel composites the
-// same splats in the same order as over the whole list (the phase-A list is the
-// nearest part of it, the phase-B list the rest), with the same operations.
-template <bool DIAG, bool FX, int SPLIT>
-__device__ __forceinline__ uint64_t blend_block(const uint32_t* __restrict__ idx, const uint4* __restrict__ rec,
-                                                uint32_t beg, uint32_t end, int bx, int by, int lane, int W,
-                                                int H, int cover_w, int cover_h, float* __restrict__ out,
-                                                float* wP, BlendDiag& dg, uint64_t* __restrict__ tmap,
-                                                float band0, uint64_t only, float* __restrict__ tsave = nullptr,
-                                                uint8_t* __restrict__ flag = nullptr,
-                                                uint32_t* __restrict__ gate = nullptr) {
-    static_assert(SPLIT == 0 || !FX, "the depth split runs the exact blend");
-    constexpr int kSlot = 24;                               // dwords per pair slot
-    const int px = bx + (lane & 7), py = by + (lane >> 3);
-    const bool inside = px < cover_w && py < cover_h;
-    const float fpx = (float)px, fpy = (float)py;
-    // transmittance; a pixel is saturated ("done", render.cu:328) iff T < 1e-3.
-    // Pixels outside the covered area start saturated (T = 0) and write 0; so do the
-    // pixels outside `only` (the exact re-blend of a fast block's suspect pixels).
-    const bool mine = ((only >> lane) & 1ull) != 0ull;
-    float T = inside && mine ? 1.0f : 0.0f;
-    f2 crg = (f2)0.0f;
-    float cb = 0.0f;
-    const float4* wP4 = reinterpret_cast<const float4*>(wP);
-    uint64_t suspect = 0;      // FX: pixels whose T decisions the band cannot vouch for
-    uint32_t ntk = 0;          // FX: splats this pixel composited so far
-    float amax = 0.0f;         // FX: largest alpha it composited
-    float tprev = 1.0f;        // FX: T before the pixel's latest composite
-    uint32_t tcount = 0, thash = 0;   // DIAG take map
-    if (SPLIT == 2 && inside) {
-        // inside => px < W and py < H (cover_w <= W, cover_h <= H)
-        const size_t o = (size_t)py * (size_t)W + (size_t)px, hw = (size_t)W * (size_t)H;
-        T = tsave[lane];
-        crg.x = out[o];
-        crg.y = out[hw + o];
-        cb = out[2 * hw + o];
-        if (DIAG && tmap) {
-            const uint64_t tm = tmap[o];
-            tcount = (uint32_t)tm;
-            thash = (uint32_t)(tm >> 32);
-        }
-    }
-
-    uint4 ra = make_uint4(0, 0, 0, 0), rb = ra, rc = ra, rd = ra;
-    uint32_t nidx = 0, cidx = 0;
-    if (beg + lane < end) {
-        cidx = idx[beg + lane];
-        const uint4* R = rec + 4 * (uint64_t)cidx;
-        ra = R[0];
-        rb = R[1];
-        rc = R[2];
-        rd = R[3];
-    }
-    if (beg + 64 + lane < end) nidx = idx[beg + 64 + lane];
-    bool alive = __ballot(!(T < 1e-3f)) != 0ull;
-    for (uint32_t base = beg; base < end && alive; base += 64) {
-        const uint32_t cnt = min(64u, end - base);
-        // ---- cull + lane masks + compaction (lane = record) ----
-        // (k_blend_aux holds a copy of this cull and of the load / prefetch around it: keep them identical)
-        // pixels not yet saturated at the batch start: T only decreases, so a record
-        // whose in-box pixels are all saturated here can never be taken in this batch
-        const uint64_t live_b = __ballot(!(T < 1e-3f));
-        // branch-free over the 64 lanes: nearly every batch has lanes on both sides of each
-        // test, so branches would only add exec-mask work (lanes >= cnt hold stale
-        // registers: their results are discarded through `valid`)
-        bool hit, fast;
-        uint32_t dsc;
-        {
-            const bool valid = (uint32_t)lane < cnt;
-            const int xmin = (int)(rc.z & 0xffffu), xmax = (int)(rc.z >> 16);
-            const int ymin = (int)(rc.w & 0xffffu), ymax = (int)(rc.w >> 16);
-            const bool box_hit = valid & !((xmax < bx) | (xmin > bx + 7) | (ymax < by) | (ymin > by + 7));
-            {
-                const float cx = __uint_as_float(rc.x), cy = __uint_as_float(rc.y);
-                const float a = __uint_as_float(ra.x), b = __uint_as_float(ra.y);
-                const float c = __uint_as_float(ra.z), e = __uint_as_float(ra.w);
-                const int x0 = max(xmin - bx, 0), x1 = min(xmax - bx, 7);
-                const int y0 = max(ymin - by, 0), y1 = min(ymax - by, 7);
-                const float dx0 = (float)(bx + x0) - cx, dx1 = (float)(bx + x1) - cx;
-                const float dy0 = (float)(by + y0) - cy, dy1 = (float)(by + y1) - cy;
-                // the box as a descriptor (box_mask: bit row * 8 + col of the block = pixel
-                // inside the AABB), expanded on the scalar unit by the compositing loop:
-                // column byte | (56 - 8 (y1 - y0)) << 8 | 8 y0 << 16
-                // (shift counts masked to the hardware's: only lanes outside the box can
-                // have them out of range, and their results are discarded)
-                const uint32_t colb = (0xffu >> ((uint32_t)(7 - (x1 - x0)) & 31u)) << ((uint32_t)x0 & 31u);
-                const uint32_t rsh = (uint32_t)(56 - 8 * (y1 - y0)) & 63u, lsh = (uint32_t)(8 * y0) & 63u;
-                dsc = colb | (rsh << 8) | (lsh << 16);
-                // the same 64-bit mask here, only for the saturation filter below
-                const uint64_t rows = (~0ull >> rsh) << lsh;
-                const uint32_t rep = __builtin_amdgcn_perm(colb, colb, 0u);   // colb in every byte
-                const uint64_t lrows = rows & live_b;
-                // cull word (cull_word): per-record parts of the block test and the proof
-                const float S = __uint_as_float(rd.w);
-                const float M = fmaxf(fmaxf(fabsf(dx0), fabsf(dx1)), fmaxf(fabsf(dy0), fabsf(dy1)));
-                const float SMM = S * M * M;
-                hit = box_hit & ((((uint32_t)lrows | (uint32_t)(lrows >> 32)) & rep) != 0u) &
-                      block_may_reach(a, b, c, e, __uint_as_float(rd.y), __uint_as_float(rd.z), dx0, dx1, dy0,
-                                      dy1, SMM, block_cut(__uint_as_float(rd.x)));
-                fast = SMM <= 4e7f;   // per-block part of the fast-path proof
-                // the fast exp's error bound assumes opacity in [0, 1] (NaN fails)
-                if (FX) fast = fast && __uint_as_float(rb.x) <= 1.0f;
-            }
-        }
-        const uint64_t m = __ballot(hit);
-        const uint32_t nsurv = (uint32_t)__popcll(m);
-        const bool all_fast = __ballot(hit & !fast) == 0ull;
-        if (FX && !all_fast) return ~0ull;   // exact re-blend of the whole block
-        if (hit) {
-            const uint32_t k = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
-                                                         __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-            float* S = wP + (k >> 1) * kSlot;
-            const int h = (int)(k & 1u);
-            S[0 + h] = __uint_as_float(rc.x);
-            S[2 + h] = __uint_as_float(rc.y);
-            // fast batches store the conic pre-scaled by -0.5 (exact, see coef_ok)
-            const float sc = all_fast ? -0.5f : 1.0f;
-            S[4 + h] = sc * __uint_as_float(ra.x);
-            S[6 + h] = sc * __uint_as_float(ra.y);
-            S[8 + h] = sc * __uint_as_float(ra.z);
-            S[10 + h] = sc * __uint_as_float(ra.w);
-            S[12 + h] = __uint_as_float(rb.x);
-            S[14 + 2 * h] = __uint_as_float(rb.y);
-            S[15 + 2 * h] = __uint_as_float(rb.z);
-            S[18 + h] = __uint_as_float(rb.w);
-            if (FX) S[20 + h] = __uint_as_float(rd.x);
-            // box descriptor (box_mask) | survivor lane << 24: the compositing loop reads
-            // both splats' from the slot instead of walking the survivor mask.  The last
-            // pair's second descriptor carries kLastPair (below)
-            S[22 + h] = __uint_as_float(dsc | ((uint32_t)lane << 24) | (k + 1u == nsurv && h ? kLastPair : 0u));
-        }
-        if ((nsurv & 1u) && lane < 11) {
-            // odd count: zero the unused second half of the last slot (descriptor 0 = empty
-            // box keeps it inert); second-half dwords of a slot: 1 3 5 7 9 11 13 | 16 17 |
-            // 19 | 23 (arithmetic, not a table: a table load would stall the wave on memory
-            // once per odd batch)
-            // (dword 23, the pair's second descriptor: kLastPair alone, an empty box)
-            wP[(nsurv >> 1) * kSlot + (lane < 7 ? 2 * lane + 1 : lane < 10 ? lane + 9 + (lane == 9) : 23)] =
-                lane == 10 ? __uint_as_float(kLastPair) : 0.0f;
-        }
-        if (DIAG) dg.loaded += cnt;
-        const float xs_l = DIAG ? __uint_as_float(rd.x) : 0.0f;   // diagnostics: xs of record `lane`
-        const uint32_t gi_l = cidx;                                // diagnostics: its Gaussian index
-        // ---- prefetch: records of batch k+1, indices of batch k+2 ----
-        if (base + 64 + lane < end) {
-            cidx = nidx;
-            const uint4* R = rec + 4 * (uint64_t)nidx;
-            ra = R[0];
-            rb = R[1];
-            rc = R[2];
-            rd = R[3];
-        }
-        if (base + 128 + lane < end) nidx = idx[base + 128 + lane];
-
-        uint64_t mm = m;
-        if (all_fast) {
-            // lanes not yet saturated; the end-of-iteration ballot of T2 is the next
-            // iteration's "!(T < 1e-3)" (render.cu:328), so it is compared once
-            uint64_t live = __ballot(!(T < 1e-3f));
-            f2 TT;
-            TT.x = T;
-            TT.y = T;
-            const uint32_t npairs = (uint32_t)__builtin_amdgcn_readfirstlane((int)((nsurv + 1u) >> 1));
-            // one exit test per pair: after the batch's last pair `live` is 0 (the threshold
-            // above; the next batch recomputes it from T), so the loop stops when the block
-            // saturates or the batch ends
-            if (npairs != 0u) {
-#pragma unroll
-            for (uint32_t j = 0; j < 32u;) {   // unrolled: the slot offsets are immediates
-                const float4 q0 = wP4[j * (kSlot / 4) + 0], q1 = wP4[j * (kSlot / 4) + 1];
-                const float4 q2 = wP4[j * (kSlot / 4) + 2], q3 = wP4[j * (kSlot / 4) + 3];
-                const float4 q4 = wP4[j * (kSlot / 4) + 4];
-                // the pair's box descriptors from the slot (one v_readfirstlane each); the
-                // 64-bit lane masks are rebuilt from them by scalar instructions.  The
-                // unused half of an odd batch's last slot holds descriptor 0: an empty box.
-                // No survivor-mask walk, no "second splat?" selects: the loop's scalar
-                // work is a co-bound of the VALU work (round 4).
-                uint32_t dd0, dd1;
-                float2 xs;
-                if (FX) {
-                    const float4 q5 = wP4[j * (kSlot / 4) + 5];
-                    xs = make_float2(q5.x, q5.y);
-                    dd0 = __float_as_uint(q5.z);
-                    dd1 = __float_as_uint(q5.w);
-                } else {
-                    const float2 dd = *reinterpret_cast<const float2*>(wP + j * kSlot + 22);
-                    dd0 = __float_as_uint(dd.x);
-                    dd1 = __float_as_uint(dd.y);
-                }
-                const uint32_t d0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)dd0);
-                const uint32_t d1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)dd1);
-                const uint64_t box0 = box_mask(d0), box1 = box_mask(d1);
-                const bool has1 = (d1 & 0xffu) != 0u;                        // diagnostics
-                const int s0 = (int)(d0 >> 24), s1 = has1 ? (int)((d1 >> 24) & 63u) : s0;
-                // render.cu:329-332, same operation order and fused multiply-adds
-                // (gsr_blend_md2), both splats at once; the conic is stored pre-scaled
-                // by -0.5, so this is -0.5f * md2 exactly
-                const f2 dx = (f2)fpx - (f2){q0.x, q0.y};
-                const f2 dy = (f2)fpy - (f2){q0.z, q0.w};
-                const f2 u = __builtin_elementwise_fma((f2){q1.x, q1.y}, dx, (f2){q1.z, q1.w} * dy);
-                const f2 v = __builtin_elementwise_fma((f2){q2.x, q2.y}, dx, (f2){q2.z, q2.w} * dy);
-                const f2 mdh = __builtin_elementwise_fma(dx, u, dy * v);
-                const f2 ee = FX ? fast_expf_x2(mdh) : gsr_blend_expf_x2(mdh);
-                const f2 al = (f2){q3.x, q3.y} * ee;
-                const float al0 = fminf(al.x, 0.99f), al1 = fminf(al.y, 0.99f);
-                // alpha tests (render.cu:335): on alpha itself, or (FX) on the exp
-                // argument against xs — the same decisions
-                bool pass0, pass1;
-                if (FX) {
-                    pass0 = !(mdh.x < xs.x);
-                    pass1 = !(mdh.y < xs.y);
-                } else {
-                    pass0 = !(al0 < 1e-3f);
-                    pass1 = !(al1 < 1e-3f);
-                }
-                // render.cu:333-340: splat 2j, then splat 2j+1 against what 2j left
-                const bool in0 = __builtin_amdgcn_inverse_ballot_w64(box0 & live);
-                const bool in1 = __builtin_amdgcn_inverse_ballot_w64(box1);
-                // (a0, a1) and (T, T1) live in register pairs, written in place, so
-                // the packed blue product needs no moves; TT.x carries T across.
-                // FX forms the take decisions as wave masks (the composited-splat
-                // count below uses them as carry-ins)
-                uint64_t t0m = 0, t1m = 0;
-                bool take0, take1;
-                f2 AA;
-                if (FX) {
-                    t0m = box0 & live & __builtin_amdgcn_ballot_w64(pass0);
-                    take0 = __builtin_amdgcn_inverse_ballot_w64(t0m);
-                    tprev = take0 ? TT.x : tprev;
-                } else {
-                    take0 = in0 & pass0;
-                }
-                AA.x = take0 ? al0 : 0.0f;
-                // T (1 - alpha) (render.cu:339); the fast blend folds it into one fma, T - T alpha
-                // with one rounding (kFxBandStep: 3 2^-24 per composite, 1 here and 2 in the
-                // exact chain)
-                TT.y = FX ? __builtin_fmaf(-TT.x, AA.x, TT.x) : TT.x * (1.0f - AA.x);
-                if (FX) {
-                    t1m = box1 & __builtin_amdgcn_ballot_w64(!(TT.y < 1e-3f)) & __builtin_amdgcn_ballot_w64(pass1);
-                    take1 = __builtin_amdgcn_inverse_ballot_w64(t1m);
-                    tprev = take1 ? TT.y : tprev;
-                } else {
-                    take1 = in1 & !(TT.y < 1e-3f) & pass1;
-                }
-                AA.y = take1 ? al1 : 0.0f;
-                // the three colour products, then rgb += (col * alpha) * T as fused
-                // multiply-adds in list order (render.cu:337, the contraction
-                // gsr_blend_md2 documents)
-                const f2 p0 = (f2){q3.z, q3.w} * AA.x;
-                const f2 p1 = pk_mul_b_hi((f2){q4.x, q4.y}, AA);     // col1 * AA.y
-                const f2 pb = (f2){q4.z, q4.w} * AA;
-                crg = pk_fma_b_lo(p0, TT, crg);                      // + (col0 * AA.x) * TT.x
-                crg = pk_fma_b_hi(p1, TT, crg);                      // + (col1 * AA.y) * TT.y
-                cb = __builtin_fmaf(pb.y, TT.y, __builtin_fmaf(pb.x, TT.x, cb));
-                if (DIAG) {
-                    // splat-iterations with no taken lane; pair-iterations in which no live
-                    // in-box lane of either splat passes the alpha test's exp argument
-                    const float xs0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xs_l), s0));
-                    const float xs1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xs_l), s1));
-                    const bool cand0 = in0 && !(mdh.x < xs0);
-                    const bool cand1 = has1 && in1 && !(TT.x < 1e-3f) && !(mdh.y < xs1);
-                    dg.zero_taken += (__ballot(take0) == 0ull ? 1 : 0) + (has1 && __ballot(take1) == 0ull ? 1 : 0);
-                    dg.no_cand_pairs += (__ballot(cand0 || cand1) == 0ull) ? 1 : 0;
-                    dg.iter += has1 ? 2 : 1;
-                    dg.active += (uint64_t)__popcll(__ballot(in0)) +
-                                (uint64_t)__popcll(__ballot(in1 & !(TT.y < 1e-3f)));
-                    dg.taken += (uint64_t)__popcll(__ballot(take0)) + (uint64_t)__popcll(__ballot(take1));
-                    const uint32_t g0 = (uint32_t)__builtin_amdgcn_readlane((int)gi_l, s0);
-                    const uint32_t g1 = (uint32_t)__builtin_amdgcn_readlane((int)gi_l, s1);
-                    tcount += (take0 ? 1u : 0u) + (take1 ? 1u : 0u);
-                    thash += (take0 ? take_mix(g0) : 0u) + (take1 ? take_mix(g1) : 0u);
-                }
-                TT.x = FX ? __builtin_fmaf(-TT.y, AA.y, TT.y) : TT.y * (1.0f - AA.y);
-                // render.cu:328 for the next pair; after the batch's last pair the threshold
-                // is ~3.4e35 (1e-3's bits | kLastPair), so the ballot is 0 and the loop ends:
-                // the batch-end test costs two scalar instructions, not a compare of j
-                const float thr = __uint_as_float(0x3a83126fu | (d1 & kLastPair));
-                const uint64_t live_new = __ballot(!(TT.x < thr));
-                if (FX) {
-                    // n += take0 + take1 as two v_addc (the take masks as carry-in);
-                    // alpha >= +0 here, so its float maximum is the u32 maximum
-                    ntk = count_lanes2(ntk, t0m, t1m);
-                    amax = __uint_as_float(max(max(__float_as_uint(amax), __float_as_uint(AA.x)),
-                                               __float_as_uint(AA.y)));
-                    // (the band checks of each pixel's T decisions run once, at the block's
-                    // end, on the latched T before its last composite: no per-iteration branch)
-                }
-                ++j;
-                live = live_new;
-                if (live == 0ull) break;
-            }
-            }
-            alive = __ballot(!(TT.x < 1e-3f)) != 0ull;   // block not yet saturated
-            T = TT.x;
-        } else {
-            // exact one-splat path (render.cu:329-340 with gsr_blend_expf and selects)
-            for (uint32_t k = 0; mm && alive; ++k) {
-                const int s = __builtin_ctzll(mm);
-                mm &= mm - 1;
-                const uint64_t box = box_mask((uint32_t)__builtin_amdgcn_readlane((int)dsc, s));
-                const float* S = wP + (k >> 1) * kSlot;
-                const int h = (int)(k & 1u);
-                const float dx = fpx - S[0 + h], dy = fpy - S[2 + h];
-                const float md = gsr_blend_md2(dx, dy, S[4 + h], S[6 + h], S[8 + h], S[10 + h]);
-                const float ee = gsr_blend_expf(-0.5f * md);
-                float alpha = S[12 + h] * ee;
-                alpha = fminf(alpha, 0.99f);
-                const bool in = __builtin_amdgcn_inverse_ballot_w64(box);
-                const bool take = in & !(T < 1e-3f) & !(alpha < 1e-3f);
-                const float wr = __builtin_fmaf(S[14 + 2 * h] * alpha, T, crg.x);
-                const float wg = __builtin_fmaf(S[15 + 2 * h] * alpha, T, crg.y);
-                const float wb = __builtin_fmaf(S[18 + h] * alpha, T, cb);
-                const float Tn = T * (1.0f - alpha);
-                if (DIAG) {
-                    dg.iter += 1;
-                    dg.slow += 1;
-                    dg.active += (uint64_t)__popcll(__ballot(in & !(T < 1e-3f)));
-                    dg.taken += (uint64_t)__popcll(__ballot(take));
-                    tcount += take ? 1u : 0u;
-                    thash += take ? take_mix((uint32_t)__builtin_amdgcn_readlane((int)gi_l, s)) : 0u;
-                }
-                crg.x = take ? wr : crg.x;
-                crg.y = take ? wg : crg.y;
-                cb = take ? wb : cb;
-                T = take ? Tn : T;
-                alive = __ballot(!(T < 1e-3f)) != 0ull;
-            }
-        }
-    }
-    if (FX) {
-        // The band checks, once per pixel.  A pixel's n, m and tprev stop changing once
-        // its T drops below 1e-3 (nothing is composited after), so at the end:
-        //  - saturated: its decisive step took T from tprev (>= 1e-3) to T (< 1e-3); the
-        //    exact chain takes the same branches if both lie outside the band (every
-        //    earlier T is >= tprev: T never increases);
-        //  - unsaturated: T must lie above the band.
-        // Pixels that started saturated (outside the cover or `only`) composited nothing.
-        const float B = fx_band(band0, ntk, amax);
-        const float hi = 1e-3f * (1.0f + B), lo = 1e-3f * (1.0f - B);
-        const bool nr = (T < 1e-3f) ? (ntk != 0u) & ((tprev < hi) | !(T < lo)) : (T < hi);
-        suspect |= __ballot(nr);
-    }
-    if (SPLIT == 1) {
-        const bool unsat = __ballot(!(T < 1e-3f)) != 0ull;
-        if (unsat) tsave[lane] = T;
-        if (lane == 0) {
-            *flag = unsat ? 1u : 0u;
-            if (unsat) atomicAdd(gate, 1u);
-        }
-        suspect = unsat ? 1ull : 0ull;   // returned: the caller flags a speculative frame
-    }
-    // FX: every pixel but the suspect ones; exact: the pixels of `only`
-    const bool write = FX ? ((suspect >> lane) & 1ull) == 0ull : mine;
-    if (write && px < W && py < H) {
-        const size_t o = (size_t)py * (size_t)W + (size_t)px;
-        const size_t hw = (size_t)W * (size_t)H;
-        out[o] = inside ? crg.x : 0.0f;
-        out[hw + o] = inside ? crg.y : 0.0f;
-        out[2 * hw + o] = inside ? cb : 0.0f;
-        if (DIAG && tmap) tmap[o] = (uint64_t)tcount | ((uint64_t)thash << 32);
-    }
-    return suspect;
-}
-
-// One-wave workgroups: workgroup g blends one 8x8 block, so a finished block
-// frees its wave slot at once (no waiting for the tile's other three waves).
-// Hardware dispatch sends workgroup g to XCD g mod 8.  bands > 1: the blocks
-// (tile-major, a tile's four blocks consecutive) are cut into bands of B
-// consecutive blocks and band j goes to XCD j mod 8, so each XCD's L2 serves runs
-// of neighbouring tiles while heavy and light image regions spread over all XCDs;
-// padding workgroups past the last block exit.  bands <= 1: one contiguous run of
-// blocks per XCD (xcd_chunk).
-// FX: fast-exp blend; a block it cannot vouch for is blended again exactly by the
-// same wave (counters[8] blocks, counters[9] suspect pixels, with diagnostics).
-// STAMPS (timeline diagnostics, no counters): counters[2 * g] = start of the
-// s_memrealtime clock (100 MHz), counters[2 * g + 1] = duration (40 bits) |
-// placement << 40 (XCC id and HW_ID's SE / SH / CU / SIMD / slot).
-// DIAG: counters[0..9], then the take map (one u64 per pixel) from counters + 16.
-// SPLIT: the depth split's phase A (1) or B (2), blend_block; phase B's workgroup 0
-// publishes the count of blocks phase A left unsaturated (sp.host_st), and every
-// workgroup returns at once when that count is 0 or its own block is saturated.
-template <bool DIAG, bool STAMPS, bool FX, int SPLIT>
-__global__ __launch_bounds__(64, 8) void k_blend_w(const uint32_t* __restrict__ idx,
-                                                 const uint2* __restrict__ ranges,
-                                                 const uint4* __restrict__ rec, int tiles_x, int tiles_y,
-                                                 int W, int H, int cover_w, int cover_h,
-                                                 float* __restrict__ out,
-                                                 unsigned long long* __restrict__ counters, int bands,
-                                                 float band0, BlendSplit sp) {
-    __shared__ float4 sP[32 * 24 / 4];
-    const int ntiles = tiles_x * tiles_y;
-    const int vb = (int)blockIdx.x;
-    if (SPLIT == 1 && vb == 0 && threadIdx.x == 0 && sp.cut.kcut) split_cut_update(sp.cut);
-    if (SPLIT == 2) {
-        const uint32_t g = *sp.gate;   // uniform
-        if (vb == 0 && threadIdx.x == 0 && sp.host_st) {
-            // a frame whose near part fell short of the split point by more than 1/16 (its
-            // threshold was extrapolated from a smaller point, split_cut_update) says
-            // nothing about that point: its tag's low half 0xffff matches no split point
-            // (<= 1000), so the controller waits for a frame with a measured threshold
-            // rather than grow twice on one miss
-            const bool short_near = sp.cut.nnear && *sp.cut.nnear < sp.cut.na - sp.cut.na / 16u;
-            sp.host_st->split_unsat = g;
-            sp.host_st->split_pm = short_near ? (sp.pm | 0xffffu) : sp.pm;
-            __threadfence_system();
-        }
-        if (g == 0u) return;
-    }
-    int L;
-    if (!blend_block_index(vb, ntiles, bands, L)) return;
-    if (SPLIT == 2 && sp.bflag[L] == 0u) return;   // saturated in phase A: its pixels are final
-    const int tile = L >> 2, sub = L & 3;
-    const int tx = tile % tiles_x, ty = tile / tiles_x;
-    const int lane = (int)(threadIdx.x & 63u);
-    uint64_t t_start = 0, place = 0;
-    if (STAMPS && lane == 0) {
-        uint32_t hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        place = ((uint64_t)(xcc & 7u) << 16) | (hw & 0xffffu);
-        t_start = __builtin_amdgcn_s_memrealtime();
-        counters[2 * vb] = t_start;
-    }
-    const uint2 rr = ranges[tile];                          // {~start, end}, zero = empty
-    const uint32_t beg = rr.y ? ~rr.x : 0u;
-    const int bx = tx * GSR_TILE_PX + (sub & 1) * 8, by = ty * GSR_TILE_PX + (sub >> 1) * 8;
-    uint64_t* tmap = DIAG ? reinterpret_cast<uint64_t*>(counters + 16) : nullptr;
-    BlendDiag dg;
-    const uint64_t redo = blend_block<DIAG, FX, SPLIT>(idx, rec, beg, rr.y, bx, by, lane, W, H, cover_w, cover_h,
-                                                       out, reinterpret_cast<float*>(sP), dg, tmap, band0, ~0ull,
-                                                       SPLIT ? sp.tbuf + 64 * (size_t)L : nullptr,
-                                                       SPLIT ? sp.bflag + L : nullptr, sp.gate);
-    if (SPLIT == 1 && redo && sp.spec_host && lane == 0) {
-        sp.spec_host->spec_miss = 1u;   // no phase B queued for this frame: it is incomplete
-        if (sp.fstatus) atomicOr(sp.fstatus, 4u);
-        __threadfence_system();
-    }
-    if (FX && redo) {
-        if (DIAG && lane == 0) {
-            atomicAdd(counters + 8, 1ull);
-            atomicAdd(counters + 9, (unsigned long long)__popcll(redo));
-        }
-        // only the suspect pixels (all of them after an aborted fast pass): the others
-        // start saturated, so the cull drops every record that misses the suspects
-        // and the wave stops once they saturate
-        blend_block<DIAG, false, 0>(idx, rec, beg, rr.y, bx, by, lane, W, H, cover_w, cover_h, out,
-                                 reinterpret_cast<float*>(sP), dg, tmap, 0.0f, redo);
-    }
-    if (STAMPS && lane == 0)
-        counters[2 * vb + 1] = ((__builtin_amdgcn_s_memrealtime() - t_start) & ((1ull << 40) - 1)) | (place << 40);
-    if (DIAG && lane == 0) {
-        if (sub == 0 && dg.loaded) atomicAdd(counters, (unsigned long long)dg.loaded);
-        atomicAdd(counters + 1, (unsigned long long)dg.iter);
-        atomicAdd(counters + 2, (unsigned long long)dg.active);
-        atomicAdd(counters + 3, (unsigned long long)dg.taken);
-        atomicAdd(counters + 4, (unsigned long long)dg.slow);
-        atomicAdd(counters + 5, (unsigned long long)dg.zero_taken);
-        atomicAdd(counters + 7, (unsigned long long)dg.no_cand_pairs);
-        atomicAdd(counters + 6, (unsigned long long)(dg.iter * 64));
-    }
-}
-
-// ------------------------------------------------------------------ auxiliary render targets
-
-// -Z of every Gaussian (gsr_render_aux's depth channel): Z is the view-space z of
-// preprocess_one — the same position (4D: at tnow, the same expression) through the same
-// mv4 — so -Z is the float whose scaled value becomes the depth key, the positive distance
-// along the view axis.  Culled Gaussians get whatever the product gives; no list holds them.
-template <bool T4D>
-__global__ __launch_bounds__(256) void k_aux_depth(const float* __restrict__ arr, int64_t stride, int64_t n,
-                                                   Frame fr, float tnow, float* __restrict__ z) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    auto A = [&](int64_t k) { return arr[k * stride + i]; };
-    float gx = A(GSR_A_X);
-    float gy = A(GSR_A_Y);
-    float gz = A(GSR_A_Z);
-    if (T4D) {
-        const float dt = tnow - A(GSR_A_TCENTER);
-        const float dt2 = dt * dt, dt3 = dt2 * dt;
-        auto m = [&](int j) { return A(GSR_A_MOTION0 + j); };
-        gx = ((gx + m(0) * dt) + m(3) * dt2) + m(6) * dt3;
-        gy = ((gy + m(1) * dt) + m(4) * dt2) + m(7) * dt3;
-        gz = ((gz + m(2) * dt) + m(5) * dt2) + m(8) * dt3;
-    }
-    const float old_xyz[4] = {gx, gy, gz, 1.0f};
-    float tmp_xyz[4];
-    mv4(fr.V, old_xyz, tmp_xyz);
-    z[i] = -tmp_xyz[2];
-}
-
-// The 8-channel kernel's feature values interleaved per Gaussian: pack[2 i] and pack[2 i + 1]
-// hold features 0-3 and 4-7 of Gaussian i (0 from nfeat on).  The arrays are planar and the
-// blend gathers by scattered Gaussian index, so each planar value costs a survivor a cache
-// line of its own; interleaved, its eight values are one 32-B piece of one line.  Coalesced
-// both ways (4 nfeat + 32 bytes per Gaussian).
-__global__ __launch_bounds__(256) void k_aux_pack(const float* __restrict__ features, int64_t n, int nfeat,
-                                                  float4* __restrict__ pack) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    float v[8];
-#pragma unroll
-    for (int f = 0; f < 8; f++) v[f] = f < nfeat ? features[(int64_t)f * n + i] : 0.0f;
-    pack[2 * i] = make_float4(v[0], v[1], v[2], v[3]);
-    pack[2 * i + 1] = make_float4(v[4], v[5], v[6], v[7]);
-}
-
-// Where k_blend_aux reads its per-Gaussian values and writes its planes (nullable each;
-// feat / features with nfeat > 0).
-struct AuxIO {
-    float* color;            // 3 planes
-    float* alpha;
-    float* depth;
-    float* feat;             // nfeat planes
-    const float* features;   // nfeat arrays of n floats (NF = 4)
-    const float4* pack;      // k_aux_pack's output (NF = 8)
-    const float* z;          // k_aux_depth's output (depth != nullptr)
-    int64_t n;
-    int nfeat;
-};
-
-// The blend with auxiliary targets (gsr_render_aux): k_blend_w's schedule — one wave64 per
-// 8x8 block, one-wave workgroups, the same block -> workgroup mapping and tile lists, the
-// same 64-record batches, prefetch and conservative cull — and, for every survivor, the
-// exact one-splat step of blend_block (gsr_blend_md2, gsr_blend_expf, selects), so each
-// pixel takes the decisions of render.cu:323-341 and the colours are the exact blend's
-// bit for bit.  Every other channel accumulates like a colour, acc = fma(v alpha, T, acc)
-// in list order: v = 1 (alpha: the accumulated coverage), v = -Z (depth, un-normalised)
-// and v = the Gaussian's feature values.  Only a surviving lane gathers its splat's -Z
-// and features (by Gaussian index; the records do not hold them): up to four from the
-// planar arrays, more from k_aux_pack's interleaved copy.
-//
-// Survivor k's slot in the wave's LDS slice (12 + NF dwords, 16-B aligned, read with
-// wave-uniform addresses):
-//   [0] cx [1] cy [2] a [3] b | [4] c [5] e [6] opacity [7] red | [8] green [9] blue
-//   [10] -Z [11] unused | [12 ..] features
-// NF = 0 / 4 / 8: 3 / 4 / 5 KiB per wave.  Eight waves per SIMD of NF = 8 would need the
-// CU's whole 160 KiB and squeeze its 13 accumulators into 64 VGPRs, so that instantiation
-// asks for six or more (with colour it compiles to 69 VGPRs: seven waves, 140 KiB, no spill); the
-// others keep k_blend_w's eight.
-// COLOR false: no colour planes (the colour accumulations drop out).
-template <int NF, bool COLOR>
-__global__ __launch_bounds__(64, NF > 4 ? 6 : 8) void k_blend_aux(const uint32_t* __restrict__ idx,
-                                                                 const uint2* __restrict__ ranges,
-                                                                 const uint4* __restrict__ rec, int tiles_x,
-                                                                 int tiles_y, int W, int H, int cover_w,
-                                                                 int cover_h, int bands, AuxIO io) {
-    constexpr int kSlot = 12 + NF;                          // dwords per survivor slot
-    constexpr int kNF = NF ? NF : 1;
-    __shared__ float4 sP[64 * kSlot / 4];
-    const int ntiles = tiles_x * tiles_y;
-    const int vb = (int)blockIdx.x;
-    int L;
-    if (!blend_block_index(vb, ntiles, bands, L)) return;
-    const int tile = L >> 2, sub = L & 3;
-    const int tx = tile % tiles_x, ty = tile / tiles_x;
-    const int lane = (int)(threadIdx.x & 63u);
-    const uint2 rr = ranges[tile];                          // {~start, end}, zero = empty
-    const uint32_t beg = rr.y ? ~rr.x : 0u, end = rr.y;
-    const int bx = tx * GSR_TILE_PX + (sub & 1) * 8, by = ty * GSR_TILE_PX + (sub >> 1) * 8;
-    const float4* wP4 = sP;
-
-    const int px = bx + (lane & 7), py = by + (lane >> 3);
-    const bool inside = px < cover_w && py < cover_h;
-    const float fpx = (float)px, fpy = (float)py;
-    // pixels outside the covered area start saturated and write 0 (blend_block)
-    float T = inside ? 1.0f : 0.0f;
-    float cr = 0.0f, cg = 0.0f, cb = 0.0f, ca = 0.0f, cz = 0.0f, cf[kNF];
-#pragma unroll
-    for (int f = 0; f < kNF; f++) cf[f] = 0.0f;
-
-    uint4 ra = make_uint4(0, 0, 0, 0), rb = ra, rc = ra, rd = ra;
-    uint32_t nidx = 0, cidx = 0;
-    if (beg + lane < end) {
-        cidx = idx[beg + lane];
-        const uint4* R = rec + 4 * (uint64_t)cidx;
-        ra = R[0];
-        rb = R[1];
-        rc = R[2];
-        rd = R[3];
-    }
-    if (beg + 64 + lane < end) nidx = idx[beg + 64 + lane];
-    bool alive = __ballot(!(T < 1e-3f)) != 0ull;
-    for (uint32_t base = beg; base < end && alive; base += 64) {
-        const uint32_t cnt = min(64u, end - base);
-        // ---- cull (lane = record): a copy of blend_block's, as are the load / prefetch around it
-        // (keep them identical): AABB vs block, the live-pixel filter, the ellipse-vs-block test ----
-        const uint64_t live_b = __ballot(!(T < 1e-3f));
-        bool hit;
-        uint32_t dsc;
-        {
-            const bool valid = (uint32_t)lane < cnt;
-            const int xmin = (int)(rc.z & 0xffffu), xmax = (int)(rc.z >> 16);
-            const int ymin = (int)(rc.w & 0xffffu), ymax = (int)(rc.w >> 16);
-            const bool box_hit = valid & !((xmax < bx) | (xmin > bx + 7) | (ymax < by) | (ymin > by + 7));
-            const float cx = __uint_as_float(rc.x), cy = __uint_as_float(rc.y);
-            const float a = __uint_as_float(ra.x), b = __uint_as_float(ra.y);
-            const float c = __uint_as_float(ra.z), e = __uint_as_float(ra.w);
-            const int x0 = max(xmin - bx, 0), x1 = min(xmax - bx, 7);
-            const int y0 = max(ymin - by, 0), y1 = min(ymax - by, 7);
-            const float dx0 = (float)(bx + x0) - cx, dx1 = (float)(bx + x1) - cx;
-            const float dy0 = (float)(by + y0) - cy, dy1 = (float)(by + y1) - cy;
-            // box descriptor (box_mask); shift counts masked to the hardware's: only lanes
-            // outside the box can have them out of range, and their results are discarded
-            const uint32_t colb = (0xffu >> ((uint32_t)(7 - (x1 - x0)) & 31u)) << ((uint32_t)x0 & 31u);
-            const uint32_t rsh = (uint32_t)(56 - 8 * (y1 - y0)) & 63u, lsh = (uint32_t)(8 * y0) & 63u;
-            dsc = colb | (rsh << 8) | (lsh << 16);
-            const uint64_t rows = (~0ull >> rsh) << lsh;
-            const uint32_t rep = __builtin_amdgcn_perm(colb, colb, 0u);   // colb in every byte
-            const uint64_t lrows = rows & live_b;
-            const float S = __uint_as_float(rd.w);
-            const float M = fmaxf(fmaxf(fabsf(dx0), fabsf(dx1)), fmaxf(fabsf(dy0), fabsf(dy1)));
-            const float SMM = S * M * M;
-            hit = box_hit & ((((uint32_t)lrows | (uint32_t)(lrows >> 32)) & rep) != 0u) &
-                  block_may_reach(a, b, c, e, __uint_as_float(rd.y), __uint_as_float(rd.z), dx0, dx1, dy0, dy1,
-                                  SMM, block_cut(__uint_as_float(rd.x)));
-        }
-        // ---- survivors, compacted in list order; each gathers its -Z and features ----
-        const uint64_t m = __ballot(hit);
-        const uint32_t k_l = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        float zv = 0.0f, fv[kNF];
-#pragma unroll
-        for (int f = 0; f < kNF; f++) fv[f] = 0.0f;
-        if (hit) {
-            if (io.z) zv = io.z[cidx];
-            if (NF == 8) {
-                const float4 p0 = io.pack[2 * (int64_t)cidx], p1 = io.pack[2 * (int64_t)cidx + 1];
-                fv[0] = p0.x; fv[1 % kNF] = p0.y; fv[2 % kNF] = p0.z; fv[3 % kNF] = p0.w;
-                fv[4 % kNF] = p1.x; fv[5 % kNF] = p1.y; fv[6 % kNF] = p1.z; fv[7 % kNF] = p1.w;
-            } else {
-#pragma unroll
-                for (int f = 0; f < NF; f++)   // padding channels repeat the last array (never stored)
-                    fv[f] = io.features[(int64_t)min(f, io.nfeat - 1) * io.n + (int64_t)cidx];
-            }
-            float4* S4 = sP + k_l * (kSlot / 4);
-            S4[0] = make_float4(__uint_as_float(rc.x), __uint_as_float(rc.y), __uint_as_float(ra.x),
-                                __uint_as_float(ra.y));
-            S4[1] = make_float4(__uint_as_float(ra.z), __uint_as_float(ra.w), __uint_as_float(rb.x),
-                                __uint_as_float(rb.y));
-        }
-        const float col_g = __uint_as_float(rb.z), col_b = __uint_as_float(rb.w);
-        // ---- prefetch: records of batch k+1, indices of batch k+2 ----
-        if (base + 64 + lane < end) {
-            cidx = nidx;
-            const uint4* R = rec + 4 * (uint64_t)nidx;
-            ra = R[0];
-            rb = R[1];
-            rc = R[2];
-            rd = R[3];
-        }
-        if (base + 128 + lane < end) nidx = idx[base + 128 + lane];
-        if (hit) {
-            // (the gathered values last: their loads were issued ahead of the prefetch)
-            float4* S4 = sP + k_l * (kSlot / 4);
-            S4[2] = make_float4(col_g, col_b, zv, 0.0f);
-            if (NF >= 4) S4[3] = make_float4(fv[0], fv[1 % kNF], fv[2 % kNF], fv[3 % kNF]);
-            if (NF >= 8) S4[4] = make_float4(fv[4 % kNF], fv[5 % kNF], fv[6 % kNF], fv[7 % kNF]);
-        }
-        // ---- the exact one-splat step over the survivors (render.cu:329-340) ----
-        uint64_t mm = m;
-        for (uint32_t k = 0; mm && alive; ++k) {
-            const int s = __builtin_ctzll(mm);
-            mm &= mm - 1;
-            const uint64_t box = box_mask((uint32_t)__builtin_amdgcn_readlane((int)dsc, s));
-            const float4 q0 = wP4[k * (kSlot / 4) + 0], q1 = wP4[k * (kSlot / 4) + 1];
-            const float4 q2 = wP4[k * (kSlot / 4) + 2];
-            const float dx = fpx - q0.x, dy = fpy - q0.y;
-            const float md = gsr_blend_md2(dx, dy, q0.z, q0.w, q1.x, q1.y);
-            const float ee = gsr_blend_expf(-0.5f * md);
-            float alpha = q1.z * ee;
-            alpha = fminf(alpha, 0.99f);
-            const bool in = __builtin_amdgcn_inverse_ballot_w64(box);
-            const bool take = in & !(T < 1e-3f) & !(alpha < 1e-3f);
-            if (COLOR) {
-                const float wr = __builtin_fmaf(q1.w * alpha, T, cr);
-                const float wg = __builtin_fmaf(q2.x * alpha, T, cg);
-                const float wb = __builtin_fmaf(q2.y * alpha, T, cb);
-                cr = take ? wr : cr;
-                cg = take ? wg : cg;
-                cb = take ? wb : cb;
-            }
-            // alpha's value is 1.0f: 1.0f * alpha is alpha exactly
-            const float wa = __builtin_fmaf(alpha, T, ca);
-            const float wz = __builtin_fmaf(q2.z * alpha, T, cz);
-            ca = take ? wa : ca;
-            cz = take ? wz : cz;
-            if (NF >= 4) {
-                const float4 q3 = wP4[k * (kSlot / 4) + 3];
-                const float v[4] = {q3.x, q3.y, q3.z, q3.w};
-#pragma unroll
-                for (int f = 0; f < 4; f++) {
-                    const float wf = __builtin_fmaf(v[f] * alpha, T, cf[f % kNF]);
-                    cf[f % kNF] = take ? wf : cf[f % kNF];
-                }
-            }
-            if (NF >= 8) {
-                const float4 q4 = wP4[k * (kSlot / 4) + 4];
-                const float v[4] = {q4.x, q4.y, q4.z, q4.w};
-#pragma unroll
-                for (int f = 0; f < 4; f++) {
-                    const float wf = __builtin_fmaf(v[f] * alpha, T, cf[(4 + f) % kNF]);
-                    cf[(4 + f) % kNF] = take ? wf : cf[(4 + f) % kNF];
-                }
-            }
-            const float Tn = T * (1.0f - alpha);
-            T = take ? Tn : T;
-            alive = __ballot(!(T < 1e-3f)) != 0ull;
-        }
-    }
-    if (px < W && py < H) {
-        const size_t o = (size_t)py * (size_t)W + (size_t)px;
-        const size_t hw = (size_t)W * (size_t)H;
-        if (COLOR) {
-            io.color[o] = inside ? cr : 0.0f;
-            io.color[hw + o] = inside ? cg : 0.0f;
-            io.color[2 * hw + o] = inside ? cb : 0.0f;
-        }
-        if (io.alpha) io.alpha[o] = inside ? ca : 0.0f;
-        if (io.depth) io.depth[o] = inside ? cz : 0.0f;
-#pragma unroll
-        for (int f = 0; f < NF; f++)
-            if (f < io.nfeat) io.feat[(size_t)f * hw + o] = inside ? cf[f] : 0.0f;
-    }
-}
-
-// Where k_blend_contrib adds its per-Gaussian statistics and writes its id plane (nullable
-// each), and the frame's overflow word (Stats::overflow).
-struct ContribIO {
-    uint32_t* count;
-    unsigned long long* weight;
-    uint32_t* wmax;
-    int32_t* id;
-    const uint32_t* overflow;
-};
-
-constexpr int kContribCount = 1, kContribWeight = 2, kContribMax = 4, kContribId = 8;
-
-// Per-Gaussian contribution statistics and the id plane (gsr_render_contrib): k_blend_aux's
-// schedule — one wave64 per 8x8 block, one-wave workgroups, the same block -> workgroup
-// mapping and tile lists, the same 64-record batches, prefetch and conservative cull — and,
-// for every survivor, the exact one-splat step (gsr_blend_md2, gsr_blend_expf, selects), so
-// each pixel takes the decisions of render.cu:323-341.  No colours: a lane keeps its T, the
-// largest weight w = fma(alpha, T, 0) it composited and that splat's Gaussian index.
-//
-// A scatter, not a composite: per survivor the wave reduces its taking lanes to one triple
-// {popcount of the take ballot, sum of rint(w 2^24), max of w's float bits} (scalar values)
-// and parks it in the survivor's RECORD lane, which still holds the Gaussian index in a
-// register (saved before the prefetch overwrites cidx).  After the batch's loop every
-// survivor lane with a non-zero count issues its own atomics: at most one per statistic per
-// (wave, surviving splat), 64 distinct addresses per instruction, never one per pixel.  All
-// three reductions are integer (the weights in fixed point: 64 values below 2^24 fit 32 bits
-// in the wave, the global sum is 64-bit), so the totals do not depend on the order in which
-// waves, frames or streams add to them.
-//
-// A frame whose overflow word is set (truncated tile lists or an incomplete depth order)
-// returns at once: it adds nothing, and the caller renders it again.
-//
-// Survivor k's slot in the wave's LDS slice (8 dwords, read with wave-uniform addresses):
-//   [0] cx [1] cy [2] a [3] b | [4] c [5] e [6] opacity [7] unused
-// WHAT: the kContrib* bits of the outputs wanted; the others' reductions drop out.
-template <int WHAT>
-__global__ __launch_bounds__(64, 8) void k_blend_contrib(const uint32_t* __restrict__ idx,
-                                                         const uint2* __restrict__ ranges,
-                                                         const uint4* __restrict__ rec, int tiles_x, int tiles_y,
-                                                         int W, int H, int cover_w, int cover_h, int bands,
-                                                         ContribIO io) {
-    constexpr bool CNT = (WHAT & kContribCount) != 0, WGT = (WHAT & kContribWeight) != 0;
-    constexpr bool MAXW = (WHAT & kContribMax) != 0, ID = (WHAT & kContribId) != 0;
-    constexpr bool STATS = CNT || WGT || MAXW;
-    __shared__ float4 sP[64 * 2];
-    if (*io.overflow) return;   // uniform: an incomplete frame adds nothing
-    const int ntiles = tiles_x * tiles_y;
-    const int vb = (int)blockIdx.x;
-    int L;
-    if (!blend_block_index(vb, ntiles, bands, L)) return;
-    const int tile = L >> 2, sub = L & 3;
-    const int tx = tile % tiles_x, ty = tile / tiles_x;
-    const int lane = (int)(threadIdx.x & 63u);
-    const uint2 rr = ranges[tile];                          // {~start, end}, zero = empty
-    const uint32_t beg = rr.y ? ~rr.x : 0u, end = rr.y;
-    const int bx = tx * GSR_TILE_PX + (sub & 1) * 8, by = ty * GSR_TILE_PX + (sub >> 1) * 8;
-    const float4* wP4 = sP;
-
-    const int px = bx + (lane & 7), py = by + (lane >> 3);
-    const bool inside = px < cover_w && py < cover_h;
-    const float fpx = (float)px, fpy = (float)py;
-    // pixels outside the covered area start saturated and composite nothing (blend_block)
-    float T = inside ? 1.0f : 0.0f;
-    float best_w = 0.0f;
-    int32_t best_i = -1;
-
-    uint4 ra = make_uint4(0, 0, 0, 0), rb = ra, rc = ra, rd = ra;
-    uint32_t nidx = 0, cidx = 0;
-    if (beg + lane < end) {
-        cidx = idx[beg + lane];
-        const uint4* R = rec + 4 * (uint64_t)cidx;
-        ra = R[0];
-        rb = R[1];
-        rc = R[2];
-        rd = R[3];
-    }
-    if (beg + 64 + lane < end) nidx = idx[beg + 64 + lane];
-    bool alive = __ballot(!(T < 1e-3f)) != 0ull;
-    for (uint32_t base = beg; base < end && alive; base += 64) {
-        const uint32_t cnt = min(64u, end - base);
-        // ---- cull (lane = record): a copy of blend_block's, as are the load / prefetch around it
-        // (keep them identical): AABB vs block, the live-pixel filter, the ellipse-vs-block test ----
-        const uint64_t live_b = __ballot(!(T < 1e-3f));
-        bool hit;
-        uint32_t dsc;
-        {
-            const bool valid = (uint32_t)lane < cnt;
-            const int xmin = (int)(rc.z & 0xffffu), xmax = (int)(rc.z >> 16);
-            const int ymin = (int)(rc.w & 0xffffu), ymax = (int)(rc.w >> 16);
-            const bool box_hit = valid & !((xmax < bx) | (xmin > bx + 7) | (ymax < by) | (ymin > by + 7));
-            const float cx = __uint_as_float(rc.x), cy = __uint_as_float(rc.y);
-            const float a = __uint_as_float(ra.x), b = __uint_as_float(ra.y);
-            const float c = __uint_as_float(ra.z), e = __uint_as_float(ra.w);
-            const int x0 = max(xmin - bx, 0), x1 = min(xmax - bx, 7);
-            const int y0 = max(ymin - by, 0), y1 = min(ymax - by, 7);
-            const float dx0 = (float)(bx + x0) - cx, dx1 = (float)(bx + x1) - cx;
-            const float dy0 = (float)(by + y0) - cy, dy1 = (float)(by + y1) - cy;
-            // box descriptor (box_mask); shift counts masked to the hardware's: only lanes
-            // outside the box can have them out of range, and their results are discarded
-            const uint32_t colb = (0xffu >> ((uint32_t)(7 - (x1 - x0)) & 31u)) << ((uint32_t)x0 & 31u);
-            const uint32_t rsh = (uint32_t)(56 - 8 * (y1 - y0)) & 63u, lsh = (uint32_t)(8 * y0) & 63u;
-            dsc = colb | (rsh << 8) | (lsh << 16);
-            const uint64_t rows = (~0ull >> rsh) << lsh;
-            const uint32_t rep = __builtin_amdgcn_perm(colb, colb, 0u);   // colb in every byte
-            const uint64_t lrows = rows & live_b;
-            const float S = __uint_as_float(rd.w);
-            const float M = fmaxf(fmaxf(fabsf(dx0), fabsf(dx1)), fmaxf(fabsf(dy0), fabsf(dy1)));
-            const float SMM = S * M * M;
-            hit = box_hit & ((((uint32_t)lrows | (uint32_t)(lrows >> 32)) & rep) != 0u) &
-                  block_may_reach(a, b, c, e, __uint_as_float(rd.y), __uint_as_float(rd.z), dx0, dx1, dy0, dy1,
-                                  SMM, block_cut(__uint_as_float(rd.x)));
-        }
-        // ---- survivors, compacted in list order ----
-        const uint64_t m = __ballot(hit);
-        const uint32_t k_l = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        if (hit) {
-            float4* S4 = sP + k_l * 2;
-            S4[0] = make_float4(__uint_as_float(rc.x), __uint_as_float(rc.y), __uint_as_float(ra.x),
-                                __uint_as_float(ra.y));
-            S4[1] = make_float4(__uint_as_float(ra.z), __uint_as_float(ra.w), __uint_as_float(rb.x), 0.0f);
-        }
-        const uint32_t gidx = cidx;   // this batch's Gaussian index of record `lane`
-        // ---- prefetch: records of batch k+1, indices of batch k+2 ----
-        if (base + 64 + lane < end) {
-            cidx = nidx;
-            const uint4* R = rec + 4 * (uint64_t)nidx;
-            ra = R[0];
-            rb = R[1];
-            rc = R[2];
-            rd = R[3];
-        }
-        if (base + 128 + lane < end) nidx = idx[base + 128 + lane];
-        // ---- the exact one-splat step over the survivors (render.cu:329-340) ----
-        uint32_t p_cnt = 0, p_sum = 0, p_max = 0;   // survivor `lane`'s reduced triple
-        uint64_t mm = m;
-        for (uint32_t k = 0; mm && alive; ++k) {
-            const int s = __builtin_ctzll(mm);
-            mm &= mm - 1;
-            const uint64_t box = box_mask((uint32_t)__builtin_amdgcn_readlane((int)dsc, s));
-            const float4 q0 = wP4[k * 2 + 0], q1 = wP4[k * 2 + 1];
-            const float dx = fpx - q0.x, dy = fpy - q0.y;
-            const float md = gsr_blend_md2(dx, dy, q0.z, q0.w, q1.x, q1.y);
-            const float ee = gsr_blend_expf(-0.5f * md);
-            float alpha = q1.z * ee;
-            alpha = fminf(alpha, 0.99f);
-            const bool in = __builtin_amdgcn_inverse_ballot_w64(box);
-            const bool take = in & !(T < 1e-3f) & !(alpha < 1e-3f);
-            const uint64_t tb = __ballot(take);
-            if (tb) {   // uniform
-                // the weight of the take: k_blend_aux's alpha channel step with ca = 0
-                const float w = __builtin_fmaf(alpha, T, 0.0f);
-                if (STATS) {
-                    const bool mine = lane == s;
-                    // (without the count output: 1 = composited at all, for the guard below)
-                    const uint32_t pc = CNT ? (uint32_t)__builtin_popcountll(tb) : 1u;
-                    p_cnt = mine ? pc : p_cnt;
-                    if (WGT) {
-                        const uint32_t fx = take ? __float2uint_rn(w * 16777216.0f) : 0u;
-                        const uint32_t sum =
-                            (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(fx, OpAdd{}), 63);
-                        p_sum = mine ? sum : p_sum;
-                    }
-                    if (MAXW) {
-                        const uint32_t mx = wave_max_u32(take ? __float_as_uint(w) : 0u);
-                        p_max = mine ? mx : p_max;
-                    }
-                }
-                if (ID) {
-                    const int32_t g = __builtin_amdgcn_readlane((int)gidx, s);
-                    const bool better = take & (w > best_w);   // strictly: the first of equals stays
-                    best_w = better ? w : best_w;
-                    best_i = better ? g : best_i;
-                }
-                const float Tn = T * (1.0f - alpha);
-                T = take ? Tn : T;
-                alive = __ballot(!(T < 1e-3f)) != 0ull;
-            }
-        }
-        // ---- one atomic per statistic per survivor that some pixel composited (lane = survivor) ----
-        if (STATS && hit && p_cnt) {
-            if (CNT) atomicAdd(io.count + gidx, p_cnt);
-            if (WGT) atomicAdd(io.weight + gidx, (unsigned long long)p_sum);
-            if (MAXW) atomicMax(io.wmax + gidx, p_max);
-        }
-    }
-    if (ID && px < W && py < H) io.id[(size_t)py * (size_t)W + (size_t)px] = inside ? best_i : -1;
-}
-
-// The upstream gradients k_blend_backward reads (W*H planes, nullable each), the planar
-// per-Gaussian gradient arrays it adds to (element [c * n + i], nullable each) and the
-// frame's overflow word.
-struct BackwardIO {
-    const float* g_image;
-    const float* g_alpha;
-    float* color;
-    float* opacity;
-    float* conic;
-    float* center;
-    int64_t n;
-    const uint32_t* overflow;
-};
-
-constexpr int kBackColor = 1, kBackOpacity = 2, kBackConic = 4, kBackCenter = 8;
-
-// Sums of NV per-lane values over the wave, jointly: v_permlane32_swap folds two values into
-// one register (lanes 0-31 then hold the first's sum over lane ^ 32, lanes 32-63 the
-// second's), v_permlane16_swap folds two of those (even rows of 16 lanes the first, odd rows
-// the second), and four row_ror adds finish inside the rows.  Afterwards every lane of row r
-// holds in x[i] the wave's total of value backward_slot(i, r) (an odd tail is paired with
-// itself, so some rows repeat a value): about NV / 2 + NV / 4 + NV adds (20 for nine values)
-// against the 6 NV of separate scans.
-template <int NV>
-__device__ __forceinline__ void wave_sum_packed(const float (&v)[NV], float (&x)[(NV + 3) / 4]) {
-    constexpr int NW = (NV + 1) / 2, NX = (NW + 1) / 2;
-    float w[NW];
-#pragma unroll
-    for (int i = 0; i < NW; i++) {
-        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[2 * i]),
-                                                        __float_as_uint(v[min(2 * i + 1, NV - 1)]), false, false);
-        w[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    }
-#pragma unroll
-    for (int i = 0; i < NX; i++) {
-        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(w[2 * i]),
-                                                        __float_as_uint(w[min(2 * i + 1, NW - 1)]), false, false);
-        float s = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-        s += __uint_as_float(dpp_u32<0x121, 0xf, true>(__float_as_uint(s)));   // row_ror:1
-        s += __uint_as_float(dpp_u32<0x122, 0xf, true>(__float_as_uint(s)));   // row_ror:2
-        s += __uint_as_float(dpp_u32<0x124, 0xf, true>(__float_as_uint(s)));   // row_ror:4
-        s += __uint_as_float(dpp_u32<0x128, 0xf, true>(__float_as_uint(s)));   // row_ror:8
-        x[i] = s;
-    }
-}
-// Which of the NV values row r holds in x[i] after wave_sum_packed, or -1 for a repeat.
-template <int NV>
-__device__ __forceinline__ int backward_slot(int i, int r) {
-    constexpr int NW = (NV + 1) / 2;
-    const int wi = 2 * i + (r & 1), vi = 2 * wi + (r >> 1);
-    return (wi < NW && vi < NV) ? vi : -1;
-}
-
-// The backward pass of the exact blend (gsr_render_backward): gradients of
-// L = sum over pixels of g_rgb . image + g_A alpha with respect to every composited splat's
-// record (colour, opacity, conic, centre), added to planar per-Gaussian arrays.
-// k_blend_contrib's schedule and decisions — one wave64 per 8x8 block, one-wave workgroups,
-// the same mapping, tile lists, 64-record batches, prefetch, conservative cull and survivor
-// compaction, the exact one-splat step, the early return on the overflow word.
-//
-// Forward order, two sweeps of the block's list in one kernel.  With u_j = g_rgb . colour_j
-// + g_A and P_j = sum_{k <= j} u_k alpha_k T_k, dL/dalpha_j = T_j u_j - (G - P_j) / (1 -
-// alpha_j), G = P_last: sweep 0 accumulates only P and leaves G, sweep 1 runs the same
-// instructions again (the sweep loop is not unrolled, so G - P_last is exactly 0) and forms
-// the gradients.  No division of T, no reversed lists.
-//
-// Per survivor that some lane takes, the wanted components (colour 3, opacity 1, conic 3 —
-// dL/db = dL/dc, one sum added to both planes — centre 2) are summed over the wave by
-// wave_sum_packed and written over the survivor's own LDS slot, which the loop has finished
-// reading; `taken` (a scalar mask) remembers which slots hold sums.  After the batch's loop
-// each such survivor's record lane reads its sums back and issues the float atomics: one per
-// component per (wave, taken splat), never one per pixel.  Their order of arrival is not
-// fixed, so the totals are not reproducible in the last bits.
-//
-// Survivor k's slot (12 dwords, read with wave-uniform addresses):
-//   [0] cx [1] cy [2] a [3] b | [4] c [5] e [6] opacity [7] r | [8] g [9] b [10..11] unused
-// WHAT: the kBack* bits of the outputs wanted; the others' sums drop out.
-template <int WHAT>
-__global__ __launch_bounds__(64, 8) void k_blend_backward(const uint32_t* __restrict__ idx,
-                                                          const uint2* __restrict__ ranges,
-                                                          const uint4* __restrict__ rec, int tiles_x, int tiles_y,
-                                                          int W, int H, int cover_w, int cover_h, int bands,
-                                                          BackwardIO io) {
-    constexpr bool COL = (WHAT & kBackColor) != 0, OPA = (WHAT & kBackOpacity) != 0;
-    constexpr bool CON = (WHAT & kBackConic) != 0, CEN = (WHAT & kBackCenter) != 0;
-    constexpr int oC = 0, oO = oC + (COL ? 3 : 0), oK = oO + (OPA ? 1 : 0), oX = oK + (CON ? 3 : 0);
-    constexpr int NV = oX + (CEN ? 2 : 0), NX = (NV + 3) / 4;
-    constexpr int kSlot = 12;
-    __shared__ float4 sP[64 * (kSlot / 4)];
-    if (*io.overflow) return;   // uniform: an incomplete frame adds nothing
-    const int ntiles = tiles_x * tiles_y;
-    const int vb = (int)blockIdx.x;
-    int L;
-    if (!blend_block_index(vb, ntiles, bands, L)) return;
-    const int tile = L >> 2, sub = L & 3;
-    const int tx = tile % tiles_x, ty = tile / tiles_x;
-    const int lane = (int)(threadIdx.x & 63u);
-    const uint2 rr = ranges[tile];                          // {~start, end}, zero = empty
-    const uint32_t beg = rr.y ? ~rr.x : 0u, end = rr.y;
-    const int bx = tx * GSR_TILE_PX + (sub & 1) * 8, by = ty * GSR_TILE_PX + (sub >> 1) * 8;
-    const float4* wP4 = sP;
-    float* wF = reinterpret_cast<float*>(sP);
-
-    const int px = bx + (lane & 7), py = by + (lane >> 3);
-    const bool inside = px < cover_w && py < cover_h;
-    const float fpx = (float)px, fpy = (float)py;
-    // the pixel's upstream gradient; pixels outside the covered area composite nothing
-    float g_r = 0.0f, g_g = 0.0f, g_b = 0.0f, g_a = 0.0f;
-    if (inside && px < W && py < H) {
-        const size_t o = (size_t)py * (size_t)W + (size_t)px;
-        const size_t hw = (size_t)W * (size_t)H;
-        if (io.g_image) {
-            g_r = io.g_image[o];
-            g_g = io.g_image[hw + o];
-            g_b = io.g_image[2 * hw + o];
-        }
-        if (io.g_alpha) g_a = io.g_alpha[o];
-    }
-
-    float G = 0.0f;
-#pragma nounroll
-    for (int sweep = 0; sweep < 2; ++sweep) {
-        // pixels outside the covered area start saturated and composite nothing (blend_block)
-        float T = inside ? 1.0f : 0.0f;
-        float P = 0.0f;
-        uint4 ra = make_uint4(0, 0, 0, 0), rb = ra, rc = ra, rd = ra;
-        uint32_t nidx = 0, cidx = 0;
-        if (beg + lane < end) {
-            cidx = idx[beg + lane];
-            const uint4* R = rec + 4 * (uint64_t)cidx;
-            ra = R[0];
-            rb = R[1];
-            rc = R[2];
-            rd = R[3];
-        }
-        if (beg + 64 + lane < end) nidx = idx[beg + 64 + lane];
-        bool alive = __ballot(!(T < 1e-3f)) != 0ull;
-        for (uint32_t base = beg; base < end && alive; base += 64) {
-            const uint32_t cnt = min(64u, end - base);
-            // ---- cull (lane = record): a copy of blend_block's, as are the load / prefetch around
-            // it (keep them identical): AABB vs block, the live-pixel filter, the ellipse-vs-block
-            // test ----
-            const uint64_t live_b = __ballot(!(T < 1e-3f));
-            bool hit;
-            uint32_t dsc;
-            {
-                const bool valid = (uint32_t)lane < cnt;
-                const int xmin = (int)(rc.z & 0xffffu), xmax = (int)(rc.z >> 16);
-                const int ymin = (int)(rc.w & 0xffffu), ymax = (int)(rc.w >> 16);
-                const bool box_hit = valid & !((xmax < bx) | (xmin > bx + 7) | (ymax < by) | (ymin > by + 7));
-                const float cx = __uint_as_float(rc.x), cy = __uint_as_float(rc.y);
-                const float a = __uint_as_float(ra.x), b = __uint_as_float(ra.y);
-                const float c = __uint_as_float(ra.z), e = __uint_as_float(ra.w);
-                const int x0 = max(xmin - bx, 0), x1 = min(xmax - bx, 7);
-                const int y0 = max(ymin - by, 0), y1 = min(ymax - by, 7);
-                const float dx0 = (float)(bx + x0) - cx, dx1 = (float)(bx + x1) - cx;
-                const float dy0 = (float)(by + y0) - cy, dy1 = (float)(by + y1) - cy;
-                // box descriptor (box_mask); shift counts masked to the hardware's: only lanes
-                // outside the box can have them out of range, and their results are discarded
-                const uint32_t colb = (0xffu >> ((uint32_t)(7 - (x1 - x0)) & 31u)) << ((uint32_t)x0 & 31u);
-                const uint32_t rsh = (uint32_t)(56 - 8 * (y1 - y0)) & 63u, lsh = (uint32_t)(8 * y0) & 63u;
-                dsc = colb | (rsh << 8) | (lsh << 16);
-                const uint64_t rows = (~0ull >> rsh) << lsh;
-                const uint32_t rep = __builtin_amdgcn_perm(colb, colb, 0u);   // colb in every byte
-                const uint64_t lrows = rows & live_b;
-                const float S = __uint_as_float(rd.w);
-                const float M = fmaxf(fmaxf(fabsf(dx0), fabsf(dx1)), fmaxf(fabsf(dy0), fabsf(dy1)));
-                const float SMM = S * M * M;
-                hit = box_hit & ((((uint32_t)lrows | (uint32_t)(lrows >> 32)) & rep) != 0u) &
-                      block_may_reach(a, b, c, e, __uint_as_float(rd.y), __uint_as_float(rd.z), dx0, dx1, dy0,
-                                      dy1, SMM, block_cut(__uint_as_float(rd.x)));
-            }
-            // ---- survivors, compacted in list order ----
-            const uint64_t m = __ballot(hit);
-            const uint32_t k_l =
-                __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-            if (hit) {
-                float4* S4 = sP + k_l * (kSlot / 4);
-                S4[0] = make_float4(__uint_as_float(rc.x), __uint_as_float(rc.y), __uint_as_float(ra.x),
-                                    __uint_as_float(ra.y));
-                S4[1] = make_float4(__uint_as_float(ra.z), __uint_as_float(ra.w), __uint_as_float(rb.x),
-                                    __uint_as_float(rb.y));
-                S4[2] = make_float4(__uint_as_float(rb.z), __uint_as_float(rb.w), 0.0f, 0.0f);
-            }
-            const uint32_t gidx = cidx;   // this batch's Gaussian index of record `lane`
-            // ---- prefetch: records of batch k+1, indices of batch k+2 ----
-            if (base + 64 + lane < end) {
-                cidx = nidx;
-                const uint4* R = rec + 4 * (uint64_t)nidx;
-                ra = R[0];
-                rb = R[1];
-                rc = R[2];
-                rd = R[3];
-            }
-            if (base + 128 + lane < end) nidx = idx[base + 128 + lane];
-            // ---- the exact one-splat step over the survivors (render.cu:329-340) ----
-            uint64_t taken = 0;   // survivors whose slot holds sums
-            uint64_t mm = m;
-            for (uint32_t k = 0; mm && alive; ++k) {
-                const int s = __builtin_ctzll(mm);
-                mm &= mm - 1;
-                const uint64_t box = box_mask((uint32_t)__builtin_amdgcn_readlane((int)dsc, s));
-                const float4 q0 = wP4[k * 3 + 0], q1 = wP4[k * 3 + 1], q2 = wP4[k * 3 + 2];
-                const float dx = fpx - q0.x, dy = fpy - q0.y;
-                const float md = gsr_blend_md2(dx, dy, q0.z, q0.w, q1.x, q1.y);
-                const float ee = gsr_blend_expf(-0.5f * md);
-                const float oe = q1.z * ee;
-                const float alpha = fminf(oe, 0.99f);
-                const bool in = __builtin_amdgcn_inverse_ballot_w64(box);
-                const bool take = in & !(T < 1e-3f) & !(alpha < 1e-3f);
-                if (__ballot(take)) {   // uniform
-                    const float u = __builtin_fmaf(g_r, q1.w, __builtin_fmaf(g_g, q2.x, __builtin_fmaf(g_b, q2.y, g_a)));
-                    const float w = alpha * T;
-                    const float Pn = __builtin_fmaf(u, w, P);
-                    P = take ? Pn : P;
-                    if (sweep) {
-                        float v[NV];
-                        const float wt = take ? w : 0.0f;
-                        if (COL) {
-                            v[oC % NV] = g_r * wt;
-                            v[(oC + 1) % NV] = g_g * wt;
-                            v[(oC + 2) % NV] = g_b * wt;
-                        }
-                        if (OPA || CON || CEN) {
-                            // (1 - alpha >= 0.01; the clamped alpha passes nothing on)
-                            float da = T * u - (G - P) * __builtin_amdgcn_rcpf(1.0f - alpha);
-                            da = (take & !(oe > 0.99f)) ? da : 0.0f;
-                            if (OPA) v[oO % NV] = da * ee;
-                            const float dmd = -0.5f * oe * da;
-                            if (CON) {
-                                v[oK % NV] = dmd * dx * dx;
-                                v[(oK + 1) % NV] = dmd * dx * dy;
-                                v[(oK + 2) % NV] = dmd * dy * dy;
-                            }
-                            if (CEN) {
-                                const float bc = q0.w + q1.x;
-                                v[oX % NV] = -dmd * (2.0f * q0.z * dx + bc * dy);
-                                v[(oX + 1) % NV] = -dmd * (bc * dx + 2.0f * q1.y * dy);
-                            }
-                        }
-                        float x[NX];
-                        wave_sum_packed<NV>(v, x);
-                        if ((lane & 15) == 0) {
-#pragma unroll
-                            for (int i = 0; i < NX; i++) {
-                                const int vi = backward_slot<NV>(i, lane >> 4);
-                                if (vi >= 0) wF[k * kSlot + vi] = x[i];
-                            }
-                        }
-                        taken |= 1ull << k;
-                    }
-                    const float Tn = T * (1.0f - alpha);
-                    T = take ? Tn : T;
-                    alive = __ballot(!(T < 1e-3f)) != 0ull;
-                }
-            }
-            // ---- one atomic per component per survivor that some pixel composited (lane = survivor) ----
-            if (sweep && hit && ((taken >> k_l) & 1ull)) {
-                const float* r = wF + k_l * kSlot;
-                const int64_t n = io.n;
-                if (COL) {
-                    atomicAdd(io.color + gidx, r[oC]);
-                    atomicAdd(io.color + n + gidx, r[oC + 1]);
-                    atomicAdd(io.color + 2 * n + gidx, r[oC + 2]);
-                }
-                if (OPA) atomicAdd(io.opacity + gidx, r[oO]);
-                if (CON) {
-                    atomicAdd(io.conic + gidx, r[oK]);
-                    atomicAdd(io.conic + n + gidx, r[oK + 1]);
-                    atomicAdd(io.conic + 2 * n + gidx, r[oK + 1]);
-                    atomicAdd(io.conic + 3 * n + gidx, r[oK + 2]);
-                }
-                if (CEN) {
-                    atomicAdd(io.center + gidx, r[oX]);
-                    atomicAdd(io.center + n + gidx, r[oX + 1]);
-                }
-            }
-        }
-        G = P;
-    }
-}
-
 // ------------------------------------------------------------------ standalone sort ABI helpers
 
 // (u32(key) << 32 | i): the reference sorts int keys as unsigned 8-bit digits
@@ -4809,45 +3332,6 @@ __global__ void k_gather_lwg(const gsr_lwg* __restrict__ in, const uint64_t* __r
     uint32_t r = (uint32_t)stage2[i];
     if (stage1) r = (uint32_t)stage1[r];
     out[i] = in[r];
-}
-
-// Exhaustive checks behind the blend's exp (gsr_exp_probe).  Over every float key k
-// in [key_lo, key_hi): viol[0] counts gsr_blend_expf(x_k) > gsr_blend_expf(x_k+1)
-// (monotonicity of the exact exp, which makes the alpha test a threshold on its
-// argument); viol[1] counts the x in [-2e7, 5] where a half of gsr_blend_expf_x2 differs
-// from gsr_blend_expf (the packed path's unclamped domain); and over the same keys the
-// largest |fast_expf / gsr_blend_expf - 1| is kept as float bits, split at x >= x_big:
-// errs[0] every key (x in the range), errs[1] x >= x_big.
-__global__ __launch_bounds__(256) void k_exp_probe(uint32_t key_lo, uint32_t key_hi, float x_big,
-                                                   unsigned long long* __restrict__ viol,
-                                                   uint32_t* __restrict__ errs) {
-    const uint64_t nthr = (uint64_t)gridDim.x * blockDim.x;
-    uint64_t bad = 0, pk_bad = 0;
-    float emax = 0.0f, ebig = 0.0f;
-    for (uint64_t k = (uint64_t)key_lo + blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; k < key_hi; k += nthr) {
-        const float x = gsr_key_float((uint32_t)k);
-        const float e = gsr_blend_expf(x);
-        const float en = gsr_blend_expf(gsr_key_float((uint32_t)k + 1u));
-        bad += e > en ? 1u : 0u;
-        f2 xx;
-        xx.x = x;
-        xx.y = -x;
-        if (x >= -2e7f && x <= 5.0f) {
-            const f2 pk = gsr_blend_expf_x2(xx);
-            pk_bad += __float_as_uint(pk.x) != __float_as_uint(e) ? 1u : 0u;
-            if (-x >= -2e7f && -x <= 5.0f)
-                pk_bad += __float_as_uint(pk.y) != __float_as_uint(gsr_blend_expf(-x)) ? 1u : 0u;
-        }
-        const float f = fast_expf_x2(xx).x;
-        const float r = (float)fabs((double)f / (double)e - 1.0);   // rounded up below
-        const float ru = __uint_as_float(__float_as_uint(r) + 1u);
-        emax = fmaxf(emax, ru);
-        if (x >= x_big) ebig = fmaxf(ebig, ru);
-    }
-    if (bad) atomicAdd(viol, (unsigned long long)bad);
-    if (pk_bad) atomicAdd(viol + 1, (unsigned long long)pk_bad);
-    atomicMax(errs, __float_as_uint(emax));
-    atomicMax(errs + 1, __float_as_uint(ebig));
 }
 
 // gsr_alpha_take_min_x on the device, one opacity per thread (tests).
@@ -5199,152 +3683,6 @@ hipError_t launch_kv_pass(const void* keys_in, const uint32_t* vals_in, void* ke
     return hipGetLastError();
 }
 
-// The grid of both blends (blend_block_index): `bands` bands of band_tiles tiles per XCD, dealt
-// round-robin; ng is padded to whole rounds.  Too small for two rounds: one run per XCD (bands 1).
-static void blend_grid(int nt, int band_tiles, int& bands, int& ng) {
-    bands = 1;
-    ng = 4 * nt;
-    if (band_tiles > 0 && (nt + 8 * band_tiles - 1) / (8 * band_tiles) > 1) {
-        bands = (nt + 8 * band_tiles - 1) / (8 * band_tiles);
-        ng = 8 * bands * ((4 * nt + 8 * bands - 1) / (8 * bands));
-    }
-}
-
-hipError_t launch_blend(const uint32_t* idx, const uint2* ranges, const uint4* rec, const Frame& fr,
-                        float* out, unsigned long long* consumed, bool stamps, int band_tiles, int blend_exp,
-                        hipStream_t s, const BlendSplit* split) {
-    // blend_exp 2 (test hook): the fast blend with a band of 100 %, so every block in
-    // which a pixel saturates (or ends below 2e-3) is blended again exactly
-    const bool fast_exp = blend_exp != 0;
-    const float band0 = blend_exp == 2 ? 1.0f : kFxBand0;
-    const int nt = fr.tiles_x * fr.tiles_y;
-    if (nt <= 0) return hipSuccess;
-    int bands, ng;
-    blend_grid(nt, band_tiles, bands, ng);
-    const int phase = split ? split->phase : 0;
-    if (phase < 0 || phase > 2 || (phase && (fast_exp || stamps || !split->tbuf || !split->bflag || !split->gate)))
-        return hipErrorInvalidValue;
-    const BlendSplit sp = split ? *split : BlendSplit{0, nullptr, nullptr, nullptr, nullptr, nullptr, {}, 0u, nullptr};
-#define GSR_BLEND_S(D, ST, FX, SP)                                                                          \
-    hipLaunchKernelGGL((k_blend_w<D, ST, FX, SP>), dim3(ng), dim3(64), 0, s, idx, ranges, rec, fr.tiles_x,  \
-                       fr.tiles_y, fr.W, fr.H, fr.cover_w, fr.cover_h, out, consumed, bands, band0, sp)
-#define GSR_BLEND(D, ST, FX) GSR_BLEND_S(D, ST, FX, 0)
-    if (phase) {
-        if (consumed) {
-            if (phase == 1) GSR_BLEND_S(true, false, false, 1);
-            else GSR_BLEND_S(true, false, false, 2);
-        } else {
-            if (phase == 1) GSR_BLEND_S(false, false, false, 1);
-            else GSR_BLEND_S(false, false, false, 2);
-        }
-    } else if (stamps && consumed) {
-        if (fast_exp) GSR_BLEND(false, true, true);
-        else GSR_BLEND(false, true, false);
-    } else if (consumed) {
-        if (fast_exp) GSR_BLEND(true, false, true);
-        else GSR_BLEND(true, false, false);
-    } else {
-        if (fast_exp) GSR_BLEND(false, false, true);
-        else GSR_BLEND(false, false, false);
-    }
-#undef GSR_BLEND
-#undef GSR_BLEND_S
-    return hipGetLastError();
-}
-
-hipError_t launch_aux_depth(const float* arrays, int64_t stride, int64_t n, const Frame& fr, bool four_d, float t,
-                            float* z, hipStream_t s) {
-    if (n <= 0) return hipSuccess;
-    const dim3 g(grid_for(n, 256));
-    if (four_d) hipLaunchKernelGGL((k_aux_depth<true>), g, dim3(256), 0, s, arrays, stride, n, fr, t, z);
-    else hipLaunchKernelGGL((k_aux_depth<false>), g, dim3(256), 0, s, arrays, stride, n, fr, t, z);
-    return hipGetLastError();
-}
-
-hipError_t launch_blend_aux(const uint32_t* idx, const uint2* ranges, const uint4* rec, const Frame& fr,
-                            float* out, float* alpha, float* depth, const float* z, const float* features,
-                            int64_t n, int nfeat, float* feat_out, float4* pack, int band_tiles,
-                            hipStream_t s) {
-    if (nfeat < 0 || nfeat > 8 || (nfeat > 0 && (!features || !feat_out)) || (depth && n > 0 && !z) ||
-        (nfeat > 4 && n > 0 && !pack) ||
-        (!out && !alpha && !depth && nfeat == 0))
-        return hipErrorInvalidValue;
-    const int nt = fr.tiles_x * fr.tiles_y;
-    if (nt <= 0) return hipSuccess;
-    int bands, ng;
-    blend_grid(nt, band_tiles, bands, ng);
-    if (nfeat > 4 && n > 0)
-        hipLaunchKernelGGL(k_aux_pack, dim3(grid_for(n, 256)), dim3(256), 0, s, features, n, nfeat, pack);
-    const AuxIO io{out, alpha, depth, feat_out, features, pack, depth ? z : nullptr, n, nfeat};
-    // features padded to 0 / 4 / 8 channels
-    auto go = [&](auto nf) {
-        constexpr int NF = decltype(nf)::value;
-        with_bool(out != nullptr, [&](auto color) {
-            hipLaunchKernelGGL((k_blend_aux<NF, decltype(color)::value>), dim3(ng), dim3(64), 0, s, idx, ranges, rec,
-                               fr.tiles_x, fr.tiles_y, fr.W, fr.H, fr.cover_w, fr.cover_h, bands, io);
-        });
-    };
-    if (nfeat == 0) go(std::integral_constant<int, 0>{});
-    else if (nfeat <= 4) go(std::integral_constant<int, 4>{});
-    else go(std::integral_constant<int, 8>{});
-    return hipGetLastError();
-}
-
-template <int WHAT>
-static void blend_contrib_go(int what, int ng, hipStream_t s, const uint32_t* idx, const uint2* ranges,
-                             const uint4* rec, const Frame& fr, int bands, const ContribIO& io) {
-    if constexpr (WHAT <= 15) {
-        if (what == WHAT)
-            hipLaunchKernelGGL((k_blend_contrib<WHAT>), dim3(ng), dim3(64), 0, s, idx, ranges, rec, fr.tiles_x,
-                               fr.tiles_y, fr.W, fr.H, fr.cover_w, fr.cover_h, bands, io);
-        else
-            blend_contrib_go<WHAT + 1>(what, ng, s, idx, ranges, rec, fr, bands, io);
-    }
-}
-
-hipError_t launch_blend_contrib(const uint32_t* idx, const uint2* ranges, const uint4* rec, const Frame& fr,
-                                uint32_t* count, unsigned long long* weight, uint32_t* wmax, int32_t* id,
-                                const uint32_t* overflow, int band_tiles, hipStream_t s) {
-    const int what = (count ? kContribCount : 0) | (weight ? kContribWeight : 0) | (wmax ? kContribMax : 0) |
-                     (id ? kContribId : 0);
-    if (!what || !overflow) return hipErrorInvalidValue;
-    const int nt = fr.tiles_x * fr.tiles_y;
-    if (nt <= 0) return hipSuccess;
-    int bands, ng;
-    blend_grid(nt, band_tiles, bands, ng);
-    const ContribIO io{count, weight, wmax, id, overflow};
-    blend_contrib_go<1>(what, ng, s, idx, ranges, rec, fr, bands, io);
-    return hipGetLastError();
-}
-
-template <int WHAT>
-static void blend_backward_go(int what, int ng, hipStream_t s, const uint32_t* idx, const uint2* ranges,
-                              const uint4* rec, const Frame& fr, int bands, const BackwardIO& io) {
-    if constexpr (WHAT <= 15) {
-        if (what == WHAT)
-            hipLaunchKernelGGL((k_blend_backward<WHAT>), dim3(ng), dim3(64), 0, s, idx, ranges, rec, fr.tiles_x,
-                               fr.tiles_y, fr.W, fr.H, fr.cover_w, fr.cover_h, bands, io);
-        else
-            blend_backward_go<WHAT + 1>(what, ng, s, idx, ranges, rec, fr, bands, io);
-    }
-}
-
-hipError_t launch_blend_backward(const uint32_t* idx, const uint2* ranges, const uint4* rec, const Frame& fr,
-                                 const float* g_image, const float* g_alpha, float* color, float* opacity,
-                                 float* conic, float* center, int64_t n, const uint32_t* overflow, int band_tiles,
-                                 hipStream_t s) {
-    const int what = (color ? kBackColor : 0) | (opacity ? kBackOpacity : 0) | (conic ? kBackConic : 0) |
-                     (center ? kBackCenter : 0);
-    if (!what || (!g_image && !g_alpha) || !overflow) return hipErrorInvalidValue;
-    const int nt = fr.tiles_x * fr.tiles_y;
-    if (nt <= 0 || n <= 0) return hipSuccess;
-    int bands, ng;
-    blend_grid(nt, band_tiles, bands, ng);
-    const BackwardIO io{g_image, g_alpha, color, opacity, conic, center, n, overflow};
-    blend_backward_go<1>(what, ng, s, idx, ranges, rec, fr, bands, io);
-    return hipGetLastError();
-}
-
 hipError_t launch_split_sat(const uint8_t* bflag, int tiles_x, int tiles_y, uint32_t* sat, const uint32_t* gate,
                             hipStream_t s) {
     if (tiles_x < 1 || tiles_x > 256 || tiles_y < 1 || tiles_y > 256 || !gate) return hipErrorInvalidValue;
@@ -5373,12 +3711,6 @@ hipError_t launch_items_from_lwg(const gsr_lwg* rec, const uint64_t* src_perm, u
 hipError_t launch_gather_lwg(const gsr_lwg* in, const uint64_t* stage1, const uint64_t* stage2, uint32_t n,
                              gsr_lwg* out, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_gather_lwg, dim3((n + 255) / 256), dim3(256), 0, s, in, stage1, stage2, n, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_exp_probe(uint32_t key_lo, uint32_t key_hi, float x_big, unsigned long long* viol, uint32_t* errs,
-                            hipStream_t s) {
-    hipLaunchKernelGGL(k_exp_probe, dim3(8192), dim3(256), 0, s, key_lo, key_hi, x_big, viol, errs);
     return hipGetLastError();
 }
 

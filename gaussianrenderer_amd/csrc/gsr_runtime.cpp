@@ -2312,7 +2312,7 @@ static int depth_passes_locked(gsr_context* c, int* passes) {
         return GSR_OK;
     }
     if (!c->depth_skip) return GSR_OK;
-    uint32_t st[4];   // same plan as the kernels (gsr_kernels.hip depth_pass_skipped)
+    uint32_t st[4];   // same plan as the kernels (gsr_device.h depth_pass_skipped)
     HIP_TRY(hipMemcpy(st, c->dstats, sizeof st, hipMemcpyDeviceToHost));
     int p = 1;
     for (; p < 4; ++p) {

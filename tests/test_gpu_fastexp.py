@@ -29,7 +29,7 @@ from test_gpu_parity import CAMS, cam_for, render_gpu
 
 pytestmark = pytest.mark.gpu
 
-# gsr_kernels.hip: kFxEps3 / kFxEps2 / kFxEps1, bounds on |alpha_fast / alpha_exact - 1|
+# gsr_blend.hip: kFxEps3 / kFxEps2 / kFxEps1, bounds on |alpha_fast / alpha_exact - 1|
 # for composited lanes / alpha > 0.5 / alpha > 0.9
 K_FX_EPS = {-6.95: 6.6e-7, -0.70: 4.8e-7, -0.11: 4.8e-7}
 ULP_PRODUCT = 2.0 ** -23          # the two roundings of op * e

@@ -15,8 +15,8 @@ HIPCC ?= $(ROCM)/bin/hipcc
 CLANG ?= $(ROCM)/lib/llvm/bin/clang
 ARCH ?= gfx950
 OUT = build/asan
-# the normal kernel objects; the top-level `make asan` builds them first and passes its list
-KOBJS ?= build/obj/gsr_kernels.o build/obj/gsr_scene_ops.o build/obj/gsr_probes.o
+# KOBJS: the normal kernel objects; the top-level `make asan` builds them first and passes its
+# list (the only one: there is no default here)
 SRC = gaussianrenderer_amd/csrc
 # host-only compiles (-x c++): the sanitizer flags apply to host code only
 SAN = -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
