@@ -23,7 +23,7 @@ import numpy as np
 from . import _native
 from ._native import (AUX_MAX_FEATURES, AuxTargets, BackwardTargets, CONTRIB_WEIGHT_ONE, Camera, ContribTargets, GsrError, LAYOUT_AOS, LAYOUT_SCENE_BLOCK, LAYOUT_SCENE_BLOCK_4D,
                       LAYOUT_SCENE_BLOCK_SH3, NUM_STAGES, PLY_SH3, PLY_TYPED, SCENE4D_NARRAYS, SCENE_NARRAYS,
-                      SCENE_SH3_NARRAYS,
+                      SCENE_SH3_NARRAYS, RecordGrads, SceneGrads,
                       SPLAT_RECORD_BYTES, STAGES, TILE_PX, check, lib)
 
 __all__ = [
@@ -31,6 +31,7 @@ __all__ = [
     "loadGaussianCudaFromPly", "preprocessCUDAGaussians", "read_ply", "write_synthetic_ply",
     "SPLAT_DTYPE", "STAGES", "TILE_PX", "lib", "AUX_MAX_FEATURES", "DisplayTarget", "display_gl_current", "preprocessCUDAGaussiansGL",
     "CONTRIB_WEIGHT_ONE", "ContribTargets", "BackwardTargets", "mask_indices", "gather_planes",
+    "RecordGrads", "SceneGrads",
 ]
 
 # gsr_read_splats record (include/gsr.h).
@@ -458,6 +459,70 @@ class Renderer:
                                        t.width_stride, t.height_stride, k, byref(bw), stream or None)
         if rc not in (_native.GSR_OK, _native.GSR_E_OVERFLOW):
             raise GsrError(rc, "gsr_render_backward")
+        return rc
+
+    def project_backward(self, scene, cam: Camera, W: int, H: int, d_color_ptr=None, d_opacity_ptr=None,
+                         d_conic_ptr=None, d_center_ptr=None, position_ptr=None, opacity_ptr=None, scale_ptr=None,
+                         rot_ptr=None, sh_ptr=None, temporal_ptr=None, k: float = 3.0, stream: int = 0,
+                         layout: int = LAYOUT_SCENE_BLOCK, n: int | None = None, time: float | None = None) -> int:
+        """Enqueue the projection's backward pass (gsr_project_backward, include/gsr.h): the record
+        gradients render_backward produced, carried on to the scene arrays; every pointer an int,
+        anything with .data_ptr(), or None.  Inputs, at least one, float32 planar [c*n + i], None
+        = zeros: d_color_ptr 3 planes, d_opacity_ptr 1, d_conic_ptr 4, d_center_ptr 2.  Outputs, at
+        least one, planar [c*n + i] and ACCUMULATED: position_ptr 3 planes, opacity_ptr 1, scale_ptr
+        3, rot_ptr 4, sh_ptr 27 (48 for an SH-3 scene), temporal_ptr 11 (4D scenes only), with
+        respect to the stored (activated) values.  Gaussians with no record or an all-zero
+        upstream are not touched.  No atomics: reproducible bit for bit.  The context's last
+        frame (readbacks, timing, the depth split's controller) is left as it was."""
+        ins = [_dev_ptr(p) for p in (d_color_ptr, d_opacity_ptr, d_conic_ptr, d_center_ptr)]
+        outs = [_dev_ptr(p) for p in (position_ptr, opacity_ptr, scale_ptr, rot_ptr, sh_ptr, temporal_ptr)]
+        if not any(ins):
+            raise ValueError("project_backward: no upstream gradient given")
+        if not any(outs):
+            raise ValueError("project_backward: no output requested")
+        ptr = scene.ptr if isinstance(scene, Scene) else int(scene)
+        n = scene.n if n is None else n
+        if isinstance(scene, Scene) and layout == LAYOUT_SCENE_BLOCK:
+            layout = scene.layout
+        if time is not None:
+            self.set_time(time)
+        rg = RecordGrads(*[p or None for p in ins])
+        sg = SceneGrads(*[p or None for p in outs])
+        check(lib().gsr_project_backward(self.ctx, ptr, layout, n, byref(cam), W, H, k, byref(rg), byref(sg),
+                                         stream or None), "gsr_project_backward")
+        return _native.GSR_OK
+
+    def render_backward_scene(self, scene, cam: Camera, W: int, H: int, grad_image_ptr=None, grad_alpha_ptr=None,
+                              scratch_ptr=None, position_ptr=None, opacity_ptr=None, scale_ptr=None, rot_ptr=None,
+                              sh_ptr=None, temporal_ptr=None, k: float = 3.0, tiling=None, stream: int = 0,
+                              layout: int = LAYOUT_SCENE_BLOCK, n: int | None = None,
+                              time: float | None = None) -> int:
+        """Enqueue one frame's whole backward pass (gsr_render_backward_scene, include/gsr.h):
+        render_backward into ten record-gradient planes, then project_backward from them into the
+        scene-array outputs (as project_backward's, ACCUMULATED, at least one).  Inputs, at least
+        one: grad_image_ptr 3*W*H float32 and grad_alpha_ptr W*H.  scratch_ptr: 10*n float32 for
+        the planes (colour 3, opacity 1, conic 4, centre 2), zeroed by the call and holding the
+        frame's record gradients afterwards; None = a workspace of the context.  A frame that
+        overflows adds nothing.  Same returns as render()."""
+        gi, ga = _dev_ptr(grad_image_ptr), _dev_ptr(grad_alpha_ptr)
+        outs = [_dev_ptr(p) for p in (position_ptr, opacity_ptr, scale_ptr, rot_ptr, sh_ptr, temporal_ptr)]
+        if not (gi or ga):
+            raise ValueError("render_backward_scene: no upstream gradient given")
+        if not any(outs):
+            raise ValueError("render_backward_scene: no output requested")
+        ptr = scene.ptr if isinstance(scene, Scene) else int(scene)
+        n = scene.n if n is None else n
+        if isinstance(scene, Scene) and layout == LAYOUT_SCENE_BLOCK:
+            layout = scene.layout
+        if time is not None:
+            self.set_time(time)
+        t = tiling or TilingInformation(1, 1, H, W)
+        sg = SceneGrads(*[p or None for p in outs])
+        rc = lib().gsr_render_backward_scene(self.ctx, ptr, layout, n, byref(cam), W, H, t.num_tile_x, t.num_tile_y,
+                                             t.width_stride, t.height_stride, k, gi or None, ga or None,
+                                             _dev_ptr(scratch_ptr) or None, byref(sg), stream or None)
+        if rc not in (_native.GSR_OK, _native.GSR_E_OVERFLOW):
+            raise GsrError(rc, "gsr_render_backward_scene")
         return rc
 
     def set_frames_in_flight(self, frames: int):

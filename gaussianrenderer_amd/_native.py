@@ -128,6 +128,31 @@ class BackwardTargets(ctypes.Structure):
     ]
 
 
+class RecordGrads(ctypes.Structure):
+    """``gsr_record_grads`` (include/gsr.h): the inputs of gsr_project_backward."""
+
+    _fields_ = [
+        ("d_color", c_void_p),
+        ("d_opacity", c_void_p),
+        ("d_conic", c_void_p),
+        ("d_center", c_void_p),
+    ]
+
+
+class SceneGrads(ctypes.Structure):
+    """``gsr_scene_grads`` (include/gsr.h): the outputs of gsr_project_backward and
+    gsr_render_backward_scene."""
+
+    _fields_ = [
+        ("d_position", c_void_p),
+        ("d_opacity", c_void_p),
+        ("d_scale", c_void_p),
+        ("d_rot", c_void_p),
+        ("d_sh", c_void_p),
+        ("d_temporal", c_void_p),
+    ]
+
+
 # (name, restype, argtypes) for every symbol of include/gsr.h and include/gsr_gl.h.
 SIGNATURES = [
     ("preprocessCUDAGaussians", None,
@@ -156,6 +181,11 @@ SIGNATURES = [
                                    c_int, c_int, c_float, POINTER(ContribTargets), c_void_p]),
     ("gsr_render_backward", c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(Camera), c_int, c_int, c_int, c_int,
                                     c_int, c_int, c_float, POINTER(BackwardTargets), c_void_p]),
+    ("gsr_project_backward", c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(Camera), c_int, c_int, c_float,
+                                     POINTER(RecordGrads), POINTER(SceneGrads), c_void_p]),
+    ("gsr_render_backward_scene", c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(Camera), c_int, c_int, c_int,
+                                          c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                                          POINTER(SceneGrads), c_void_p]),
     ("gsr_render_path", c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(Camera), c_void_p, c_int, c_int,
                                 c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     ("gsr_render_path_ex", c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(Camera), c_void_p, c_int, c_int,

@@ -1,6 +1,6 @@
 // gsr_internal.h — shared between the host runtime (gsr_runtime.cpp) and the
 // gfx950 kernels (gsr_kernels.hip, gsr_blend.hip, gsr_blend_derived.hip, gsr_scene_ops.hip,
-// gsr_probes.hip).  Not part of the public ABI.
+// gsr_project.hip, gsr_probes.hip).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,6 +9,9 @@
 #include <mutex>
 
 #include "gsr_types.h"
+
+struct gsr_record_grads;   // include/gsr.h
+struct gsr_scene_grads;
 
 namespace gsr {
 
@@ -253,6 +256,14 @@ hipError_t launch_blend_backward(const uint32_t* idx, const uint2* ranges, const
                                  const float* g_image, const float* g_alpha, float* color, float* opacity,
                                  float* conic, float* center, int64_t n, const uint32_t* overflow, int band_tiles,
                                  hipStream_t s);
+// Backward pass of the projection (gsr_project_backward; k_project_backward, gsr_project.hip):
+// the record gradients `in` (planes of n floats, NULL = zeros) carried on to the scene-array
+// gradients `out` (ACCUMULATED, one thread per Gaussian, no atomics).  arrays / stride /
+// four_d / sh3 / t as given to launch_preprocess; of fr it reads the camera, W, H and znear.
+// Launch geometry from n alone; n == 0 launches nothing.
+hipError_t launch_project_backward(const float* arrays, int64_t stride, int64_t n, const Frame& fr, bool four_d,
+                                   bool sh3, float t, const gsr_record_grads& in, const gsr_scene_grads& out,
+                                   hipStream_t s);
 // Stable partition of the preprocess items: visible first, culled last (both in
 // index order), visible count into *n_live; culled tail to out only, with dead
 // rects in srect (gsr_kernels.hip "live partition").  counts: groups words.

@@ -578,6 +578,8 @@ struct gsr_context {
                                      // GSR_TUNE_DEPTH_SPLIT_STATE reads this, the state of the frame before it
     float* aux_z = nullptr;          // gsr_render_aux: -Z per Gaussian (the depth channel's values)
     int64_t aux_z_cap = 0;
+    float* rec_grads = nullptr;      // gsr_render_backward_scene without a caller's scratch: ten planes of n floats
+    int64_t rec_grads_cap = 0;
     float4* aux_pack = nullptr;      // gsr_render_aux, nfeat > 4: the features interleaved per Gaussian
     int64_t aux_pack_cap = 0;
     int fail_frame = 0;              // GSR_TUNE_FAIL_FRAME: gsr_render_path fails this frame (> 0) once
@@ -982,13 +984,12 @@ int check_overflow(gsr_context* c, bool blocking) {
                    (unsigned)s.depth_passes, c->passes_launched);
 }
 
-int fill_frame(gsr_context* c, const gsr_camera* cam, int W, int H, int nx, int ny, int ws, int hs, float k) {
+int fill_frame(Frame& f, const gsr_camera* cam, int W, int H, int nx, int ny, int ws, int hs, float k) {
     if (!cam) return set_err(GSR_E_ARG, "null camera");
     if (W <= 0 || H <= 0 || W > 32768 || H > 32768)
         return set_err(GSR_E_ARG, "image size %dx%d out of range [1, 32768]", W, H);
     if (nx <= 0 || ny <= 0 || ws <= 0 || hs <= 0)
         return set_err(GSR_E_ARG, "bad tiling nx=%d ny=%d ws=%d hs=%d", nx, ny, ws, hs);
-    Frame& f = c->fr;
     std::memcpy(f.V, cam->V_matrix, sizeof f.V);
     std::memcpy(f.P, cam->P_matrix, sizeof f.P);
     std::memcpy(f.Rc, cam->r_cam, sizeof f.Rc);
@@ -1003,6 +1004,16 @@ int fill_frame(gsr_context* c, const gsr_camera* cam, int W, int H, int nx, int 
     f.cover_h = (int)std::min<int64_t>((int64_t)ny * hs, H);
     f.tiles_x = (W + GSR_TILE_PX - 1) / GSR_TILE_PX;
     f.tiles_y = (H + GSR_TILE_PX - 1) / GSR_TILE_PX;
+    return GSR_OK;
+}
+
+// The scene arguments every frame entry point refuses.
+int check_scene_args(const void* scene, int layout, int64_t n) {
+    if (n < 0 || n > INT32_MAX) return set_err(GSR_E_ARG, "Gaussian count %lld out of range", (long long)n);
+    if (n > 0 && !scene) return set_err(GSR_E_ARG, "null scene");
+    if (layout != GSR_LAYOUT_SCENE_BLOCK && layout != GSR_LAYOUT_AOS && layout != GSR_LAYOUT_SCENE_BLOCK_4D &&
+        layout != GSR_LAYOUT_SCENE_BLOCK_SH3)
+        return set_err(GSR_E_ARG, "unknown scene layout %d", layout);
     return GSR_OK;
 }
 
@@ -1039,7 +1050,8 @@ extern "C" void gsr_destroy(gsr_context* c) {
                     (void*)c->ranges, (void*)c->soa_tmp, (void*)c->out_tmp, (void*)c->consumed, (void*)c->binmeta,
                     (void*)c->cbins, (void*)c->srect, (void*)c->spans, (void*)c->nlive, (void*)c->tbuf,
                     (void*)c->bflag, (void*)c->gate, (void*)c->kcut, (void*)c->dstats_far, (void*)c->kcut_frame,
-                    (void*)c->src_items, (void*)c->sat, (void*)c->nfar, (void*)c->bkt_rec, (void*)c->aux_z, (void*)c->aux_pack})
+                    (void*)c->src_items, (void*)c->sat, (void*)c->nfar, (void*)c->bkt_rec, (void*)c->aux_z, (void*)c->aux_pack,
+                    (void*)c->rec_grads})
         if (p) (void)hipFree(p);
     if (c->hstats) (void)hipHostFree(c->hstats);
     if (c->done_ev) (void)hipEventDestroy(c->done_ev);
@@ -1063,12 +1075,8 @@ extern "C" int gsr_reserve(gsr_context* c, int64_t n, int64_t pairs) {
 // rects, spans, partial records).  Launches nothing but the AoS transpose.
 static int preprocess_plan(gsr_context* c, const void* scene, int layout, int64_t n, const gsr_camera* cam,
                            int W, int H, int nx, int ny, int ws, int hs, float k, void* stream) {
-    if (n < 0 || n > INT32_MAX) return set_err(GSR_E_ARG, "Gaussian count %lld out of range", (long long)n);
-    if (n > 0 && !scene) return set_err(GSR_E_ARG, "null scene");
-    if (layout != GSR_LAYOUT_SCENE_BLOCK && layout != GSR_LAYOUT_AOS && layout != GSR_LAYOUT_SCENE_BLOCK_4D &&
-        layout != GSR_LAYOUT_SCENE_BLOCK_SH3)
-        return set_err(GSR_E_ARG, "unknown scene layout %d", layout);
-    if (int rc = fill_frame(c, cam, W, H, nx, ny, ws, hs, k)) return rc;
+    if (int rc = check_scene_args(scene, layout, n)) return rc;
+    if (int rc = fill_frame(c->fr, cam, W, H, nx, ny, ws, hs, k)) return rc;
     if (int rc = ensure_static(c)) return rc;
     int rc_over = check_overflow(c, false);
     if (rc_over != GSR_OK && rc_over != GSR_E_OVERFLOW) return rc_over;
@@ -1837,6 +1845,88 @@ extern "C" int gsr_render_backward(gsr_context* c, const void* scene, int layout
     std::lock_guard<std::mutex> lk(c->mu);
     return aux_frame_locked(c, scene, layout, n, cam, W, H, nx, ny, ws, hs, k, stream,
                             [&] { return blend_backward_locked(c, *bw); });
+}
+
+// ------------------------------------------------------------------ projection backward
+
+namespace {
+
+// What gsr_project_backward and gsr_render_backward_scene refuse beyond a frame's arguments.
+int check_scene_grads(const char* who, const gsr_scene_grads* out, int layout) {
+    if (!out) return set_err(GSR_E_ARG, "%s: null outputs", who);
+    if (!out->d_position && !out->d_opacity && !out->d_scale && !out->d_rot && !out->d_sh && !out->d_temporal)
+        return set_err(GSR_E_ARG, "%s: no output", who);
+    if (layout == GSR_LAYOUT_AOS)
+        return set_err(GSR_E_ARG, "%s: GSR_LAYOUT_AOS has no gradient planes; upload a scene block", who);
+    if (out->d_temporal && layout != GSR_LAYOUT_SCENE_BLOCK_4D)
+        return set_err(GSR_E_ARG, "%s: d_temporal needs a 4D scene block", who);
+    return GSR_OK;
+}
+
+int project_backward_launch(const gsr_context* c, const void* scene, int layout, int64_t n, const Frame& fr,
+                            const gsr_record_grads& in, const gsr_scene_grads& out, hipStream_t s) {
+    if (n == 0) return GSR_OK;
+    const float* arrays = reinterpret_cast<const float*>(static_cast<const char*>(scene) + GSR_SCENE_HEADER_BYTES);
+    HIP_TRY(gsr::launch_project_backward(arrays, scene_stride(n), n, fr, layout == GSR_LAYOUT_SCENE_BLOCK_4D,
+                                         layout == GSR_LAYOUT_SCENE_BLOCK_SH3, c->time, in, out, s));
+    return GSR_OK;
+}
+
+// The fused call's ten record-gradient planes (10 n floats), grown like aux_z.
+int ensure_rec_grads(gsr_context* c, int64_t n) {
+    if (10 * n <= c->rec_grads_cap) return GSR_OK;
+    const int64_t cap = 10 * std::max<int64_t>(n, 1024);
+    HIP_TRY(hipDeviceSynchronize());
+    if (int rc = realloc_dev(&c->rec_grads, (size_t)cap)) return rc;
+    c->rec_grads_cap = cap;
+    return GSR_OK;
+}
+
+}  // namespace
+
+extern "C" int gsr_project_backward(gsr_context* c, const void* scene, int layout, int64_t n, const gsr_camera* cam,
+                                    int W, int H, float k, const gsr_record_grads* in, const gsr_scene_grads* out,
+                                    void* stream) {
+    if (!c) return set_err(GSR_E_ARG, "null context");
+    if (!in) return set_err(GSR_E_ARG, "gsr_project_backward: null inputs");
+    if (!in->d_color && !in->d_opacity && !in->d_conic && !in->d_center)
+        return set_err(GSR_E_ARG, "gsr_project_backward: no upstream gradient");
+    if (int rc = check_scene_grads("gsr_project_backward", out, layout)) return rc;
+    if (int rc = check_scene_args(scene, layout, n)) return rc;
+    // a frame of its own: the context's (the last rendered frame's) is left alone
+    Frame fr;
+    if (int rc = fill_frame(fr, cam, W, H, 1, 1, W, H, k)) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return project_backward_launch(c, scene, layout, n, fr, *in, *out, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int gsr_render_backward_scene(gsr_context* c, const void* scene, int layout, int64_t n,
+                                         const gsr_camera* cam, int W, int H, int nx, int ny, int ws, int hs, float k,
+                                         const float* d_grad_image, const float* d_grad_alpha, float* d_scratch,
+                                         const gsr_scene_grads* out, void* stream) {
+    if (!c) return set_err(GSR_E_ARG, "null context");
+    if (!d_grad_image && !d_grad_alpha)
+        return set_err(GSR_E_ARG, "gsr_render_backward_scene: no upstream gradient");
+    if (int rc = check_scene_grads("gsr_render_backward_scene", out, layout)) return rc;
+    if (int rc = check_scene_args(scene, layout, n)) return rc;
+    {
+        Frame probe;   // the frame's argument errors, before the planes are zeroed
+        if (int rc = fill_frame(probe, cam, W, H, nx, ny, ws, hs, k)) return rc;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    float* planes = d_scratch;
+    if (!planes && n > 0) {
+        if (int rc = ensure_rec_grads(c, n)) return rc;
+        planes = c->rec_grads;
+    }
+    if (n > 0) HIP_TRY(hipMemsetAsync(planes, 0, 10 * (size_t)n * sizeof(float), static_cast<hipStream_t>(stream)));
+    const gsr_backward_targets bw{d_grad_image, d_grad_alpha, planes, planes + 3 * n, planes + 4 * n, planes + 8 * n};
+    const int rc = aux_frame_locked(c, scene, layout, n, cam, W, H, nx, ny, ws, hs, k, stream,
+                                    [&] { return blend_backward_locked(c, bw); });
+    if (rc != GSR_OK && rc != GSR_E_OVERFLOW) return rc;
+    const gsr_record_grads in{planes, planes + 3 * n, planes + 4 * n, planes + 8 * n};
+    if (int r2 = project_backward_launch(c, scene, layout, n, c->fr, in, *out, c->stream)) return r2;
+    return rc;
 }
 
 // ------------------------------------------------------------------ frames in flight

@@ -241,7 +241,7 @@ int gsr_render_contrib(gsr_context* ctx, const void* d_scene, int layout, int64_
  * Gaussian's SPLAT RECORD — the colour, opacity, 2D conic (inv_covar[0..3] = a, b, c, e) and
  * 2D centre (px_x, px_y) that the preprocess hands to the blend.  Carrying these on to the
  * scene's position, scale, rotation and SH arrays (the projection's backward) is not part of
- * this call.  No image is written: the call runs its own blend kernel over the tile lists.
+ * this call: gsr_project_backward does it, gsr_render_backward_scene both.  No image is written: the call runs its own blend kernel over the tile lists.
  *
  * With upstream gradients g = (g_r, g_g, g_b) = d_grad_image and g_A = d_grad_alpha at every
  * pixel (a NULL input counts as zeros), the function differentiated is
@@ -288,6 +288,96 @@ typedef struct gsr_backward_targets {
 int gsr_render_backward(gsr_context* ctx, const void* d_scene, int layout, int64_t n, const gsr_camera* cam,
                         int W, int H, int num_tile_x, int num_tile_y, int width_stride, int height_stride,
                         float k, const gsr_backward_targets* bw, void* stream);
+
+/* Backward pass of the projection: carries gsr_render_backward's record gradients on to the
+ * scene arrays a .ply stores — position, opacity, scale, rotation, SH, and the temporal arrays
+ * of a 4D block.  With it the chain render -> gsr_render_backward -> gsr_project_backward gives
+ * dL/d scene for fine-tuning, or re-fitting after a prune (gsr_gather_planes cuts the planes).
+ *
+ * The function differentiated is the preprocess's map from Gaussian i's scene arrays to its
+ * splat record, taken as a real-valued function:
+ *   p       the stored position; for a 4D block the position at gsr_set_time's t, dt = t -
+ *           trbf_center, p = x + m0 dt + m3 dt^2 + m6 dt^3 (y, z with m1/m4/m7, m2/m5/m8)
+ *   v       = V [p, 1] = (X, Y, Z, .), clip = P v, ndc = clip.xyz / clip.w; V and P are taken
+ *           as general row-major 4x4 matrices
+ *   centre  = ((ndc_x + 1) W/2, (ndc_y + 1) H/2); the record holds round() of it, and the
+ *           rounding is differentiated as the identity (straight-through): the contract
+ *           gsr_render_backward states for its d_center
+ *   Sigma   = (R S)(R S)^T, R from the normalised quaternion, S = diag(scale); Sigma_c = Rc
+ *           Sigma Rc^T with the camera's r_cam
+ *   J       = [[fx/Z, 0, -fx X/Z^2], [0, fy/Z, -fy Y/Z^2]], fx, fy of gsr_camera_intrinsics
+ *   M       = D o (J Sigma_c J^T), D the pixel factors (W/2)^2, (W/2)(H/2), (H/2)(W/2), (H/2)^2
+ *   conic   (a, b, c, e) = (M11, -M01, -M10, M00) / det M, that is [[a, b], [c, e]] = M^-1; b
+ *           and c are separate record fields with separate gradients (not symmetrised)
+ *   colour  dir = (p - camera position) / |.| (zero when the norm is <= 1e-8); SH bands 0..2
+ *           plus 0.5, clamped to [0, 1] — an SH-3 block: bands 0..3, clamped at 0 only; the
+ *           clamp passes gradient only where the unclamped value lies strictly inside; the
+ *           colour's dependence on the position through dir is part of d_position
+ *   opacity the stored value; for a 4D block times exp(-(dt / trbf_scale)^2), with gradients
+ *           to the opacity, trbf_center, trbf_scale and, through p, the nine motion arrays
+ * The extent, the pixel box, the tile rects, the depth key, k, every cull decision and the
+ * camera get no gradient.  The gradients are with respect to the STORED values (the activated
+ * opacity and scales of the scene block): a caller that optimises raw .ply values multiplies
+ * by op (1 - op) and by the scale itself.
+ *
+ * Inputs (gsr_record_grads) are gsr_render_backward's outputs, planar [c * n + i]; a NULL
+ * plane group counts as zeros.  Outputs (gsr_scene_grads), planar [c * n + i] in the array
+ * order of the scene block, ACCUMULATE and are never cleared by the library; an output that is
+ * not asked for is not computed.
+ *
+ * A Gaussian takes part when its record is defined and its upstream is not all zero:
+ *   - skipped, on the preprocess's own float32 comparisons: non-finite view position or ndc,
+ *     Z >= -nearClip, ndc z outside [-1, 1], det M non-finite or < 1e-8;
+ *   - skipped, before its scene arrays are loaded: all ten upstream entries +-0.
+ * A skipped Gaussian is not touched at all.  The screen-extent reject and the 4D temporal cull
+ * are not evaluated again: what they drop never composites and arrives with zero upstream.
+ *
+ * One thread owns one Gaussian and adds to each plane with a plain load, add and store, no
+ * atomics: for given inputs the results ARE reproducible bit for bit (unlike
+ * gsr_render_backward's).  Stream-ordered: no allocation, no synchronisation.  The context
+ * gives the lock and the 4D time only; its records, tile lists, depth-split controller, timing
+ * and diagnostics stay exactly as they were, and a readback after this call still refers to
+ * the last rendered frame.  Not offered through gsr_render_path.
+ * GSR_E_ARG, before any device work: ctx, in or out NULL; every input NULL or every output
+ * NULL; GSR_LAYOUT_AOS (gradient planes of an AoS array have no consumer here); d_temporal on
+ * a block that is not 4D; the frame arguments gsr_render refuses (camera, image size, n,
+ * scene, layout). */
+typedef struct gsr_record_grads {      /* inputs: gsr_render_backward's outputs, planar [c*n + i]; NULL = zeros */
+    const float* d_color;    /* 3 planes */
+    const float* d_opacity;  /* 1 */
+    const float* d_conic;    /* 4: a, b, c, e */
+    const float* d_center;   /* 2 */
+} gsr_record_grads;
+typedef struct gsr_scene_grads {       /* outputs, planar [c*n + i], ACCUMULATED, NULL = not computed */
+    float* d_position;  /* 3 planes: arrays 0..2 */
+    float* d_opacity;   /* 1: array 3 (the stored, activated value) */
+    float* d_scale;     /* 3: arrays 4..6 (stored, activated) */
+    float* d_rot;       /* 4: arrays 7..10 (raw w,x,y,z, through the normalisation) */
+    float* d_sh;        /* 27 planes (48 for an SH-3 block), array order of the block */
+    float* d_temporal;  /* 11 planes: trbf_center, trbf_scale (stored), motion_0..8; 4D blocks only */
+} gsr_scene_grads;
+int gsr_project_backward(gsr_context* ctx, const void* d_scene, int layout, int64_t n, const gsr_camera* cam,
+                         int W, int H, float k, const gsr_record_grads* in, const gsr_scene_grads* out, void* stream);
+
+/* The whole backward of one frame in one call: gsr_render_backward's frame into ten
+ * record-gradient planes, then gsr_project_backward from them into `out`.
+ * The planes (colour 3, opacity 1, conic 4, centre 2, each n floats, in this order) sit in
+ * d_record_scratch, or, when that is NULL, in a workspace of the context (10 n floats, grown
+ * by high-water mark: the only allocation).  The call zeroes them on `stream` first; a
+ * caller's scratch holds the frame's record gradients afterwards (the densification criterion
+ * reads its centre planes).
+ * Frame policy, GSR_E_OVERFLOW reporting and gsr_sync are gsr_render_backward's.  An
+ * incomplete frame adds nothing to `out`: its blend adds nothing, the planes stay zero and
+ * every Gaussian is skipped; render it again.  The blend's atomics make the planes, and with
+ * them `out`, differ in the last bits from run to run; for given planes the projection is
+ * reproducible.  GSR_E_ARG, before any device work: ctx or out NULL, both gradient inputs
+ * NULL, every output NULL, GSR_LAYOUT_AOS, d_temporal on a block that is not 4D, the frame
+ * arguments gsr_render refuses. */
+int gsr_render_backward_scene(gsr_context* ctx, const void* d_scene, int layout, int64_t n, const gsr_camera* cam,
+                              int W, int H, int num_tile_x, int num_tile_y, int width_stride, int height_stride, float k,
+                              const float* d_grad_image, const float* d_grad_alpha,
+                              float* d_record_scratch /* 10 planes of n floats, or NULL */,
+                              const gsr_scene_grads* out, void* stream);
 
 /* Offline camera path (config 4 on one GPU; the reference has no batch entry
  * point — it renders one frame per preprocessCUDAGaussians call, render.cu:871):
