@@ -237,6 +237,11 @@ CASES = {
     # REGION (12 x 10 pixels over a corner of four tiles), which keeps the reference to a few
     # seconds; its ambiguous pixels are zeroed like any others.
     "overflow": dict(scene="overflow", cam={}, W=640, H=480, region=(314, 325, 235, 244)),
+    # _wide_scenes' tilted scene: random quaternions and scales of 0.02 - 0.5, so the conics
+    # have off-diagonal terms of their own (the dense scenes' quaternion is the identity) and
+    # the ellipses cross many blocks at an angle; with k = 8 the boxes cover the frame
+    "tilted": dict(scene="tilted", cam={}, W=70, H=52),
+    "tilted_k8": dict(scene="tilted", cam=1, W=90, H=70, k=8.0),
 }
 # (case, upstream gradient: seed, ones, image given, alpha given) of every GPU comparison
 RUNS = [
@@ -246,6 +251,7 @@ RUNS = [
     ("sparse_b", (9, False, True, True)), ("sparse_b", (0, True, True, True)),
     ("dense99", (10, False, True, True)), ("dense_partial", (11, False, True, True)),
     ("4d", (12, False, True, True)), ("faint", (13, False, True, True)), ("overflow", (14, False, True, True)),
+    ("tilted", (15, False, True, True)), ("tilted_k8", (16, False, True, True)),
 ]
 
 _scenes, _refs = {}, {}
@@ -255,6 +261,7 @@ def scenes(gsr, orc, tmp_path_factory):
     """name -> the scene's arrays ((38, n), or (49, n) for "4d")."""
     if not _scenes:
         from test_gpu_contrib import dense_soa
+        from _wide_scenes import scene as wide_scene
         d = tmp_path_factory.mktemp("backward_scenes")
         p = str(d / "sparse.ply")
         gsr.write_synthetic_ply(p, 2000, 1)
@@ -263,7 +270,8 @@ def scenes(gsr, orc, tmp_path_factory):
         d99 = dense_soa()
         d99[3] = 0.99
         _scenes.update({"dense": dense_soa(), "dense99": d99, "sparse": gsr.read_ply(p),
-                        "4d": gsr.read_ply(p4, four_d=True), "overflow": overflow_soa()})
+                        "4d": gsr.read_ply(p4, four_d=True), "overflow": overflow_soa(),
+                        "tilted": wide_scene("tilted")})
     return _scenes
 
 

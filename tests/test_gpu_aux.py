@@ -23,6 +23,9 @@ SIZES = [(640, 480), (333, 217), (37, 23), (1, 1)]
 # the image edge, saturated and never-saturated pixels, empty tiles
 CASES = [(640, 480, ci) for ci in range(len(CAMS))] + [(W, H, 1) for W, H in SIZES[1:]]
 TILINGS = [(8, 8, 40, 30), (7, 3, 92, 160)]
+# ... and _wide_scenes' tilted scene from camera 0 (the third entry names the scene): random
+# quaternions, so the conics carry off-diagonal terms of their own, up to 81 takes per pixel
+WIDE_CASES = [(128, 80, "tilted")]
 F_DC, F_REST = slice(11, 14), slice(14, 38)
 
 
@@ -63,13 +66,33 @@ def random_soa(soa, seed=7):
 _refs = {}
 
 
+def cam_of(gsr, W, H, ci):
+    """The camera of a case: CAMS[ci], or camera 0 where ci names a scene of WIDE_CASES."""
+    return cam_for(gsr, W, H, **CAMS[ci if isinstance(ci, int) else 0])
+
+
+@pytest.fixture(scope="module")
+def scene_of(gpu, c1, scene1):
+    """ci -> (arrays, scene) of a case: config 1, or the scene that ci names."""
+    cache = {}
+
+    def get(ci):
+        if isinstance(ci, int):
+            return c1, scene1
+        if ci not in cache:
+            from _wide_scenes import scene as wide_scene
+            cache[ci] = (wide_scene(ci), gpu.Scene.from_soa(wide_scene(ci)))
+        return cache[ci]
+    return get
+
+
 def oracle(orc, gsr, kind, soa, W, H, ci, tiling=None):
     """The oracle's images, computed once per module: 'rgb' the scene's, 'ones' channel 0 of
     the all-ones recolouring (= alpha), 'rand' the random recolouring's, with the
     preprocessed colours (3, n) that make it up."""
     key = (kind, W, H, ci, tiling)
     if key not in _refs:
-        cam = cam_for(gsr, W, H, **CAMS[ci])
+        cam = cam_of(gsr, W, H, ci)
         if kind == "rgb":
             _refs[key] = orc.render(soa, cam, W, H, 3.0, tiling=tiling)
         elif kind == "ones":
@@ -136,12 +159,13 @@ def plain(gsr, torch, scene, cam, W, H, renderer):
 
 # ---------------------------------------------------------------- 1. colour, 2. alpha
 
-@pytest.mark.parametrize("W,H,ci", CASES)
-def test_colour_and_alpha_match_oracle(gpu, orc, torch, c1, scene1, W, H, ci):
+@pytest.mark.parametrize("W,H,ci", CASES + WIDE_CASES)
+def test_colour_and_alpha_match_oracle(gpu, orc, torch, scene_of, W, H, ci):
     """d_out is the oracle's image bit for bit with knob 22 at its default (aux frames
     always run the exact blend); alpha is the oracle's image of an all-ones colour; a plain
     render() on the same context afterwards is unaffected."""
-    cam = cam_for(gpu, W, H, **CAMS[ci])
+    c1, scene1 = scene_of(ci)
+    cam = cam_of(gpu, W, H, ci)
     r = gpu.Renderer()
     got = aux(gpu, torch, scene1, cam, W, H, renderer=r)
     want = oracle(orc, gpu, "rgb", c1, W, H, ci)
@@ -173,19 +197,20 @@ def test_features_match_recoloured_oracle(gpu, orc, torch, c1, scene1, W, H, ci,
 # ---------------------------------------------------------------- 4. depth
 
 def depth_values(orc, gsr, soa, W, H, ci):
-    spl = orc.preprocess(soa, cam_for(gsr, W, H, **CAMS[ci]), W, H, 3.0)
+    spl = orc.preprocess(soa, cam_of(gsr, W, H, ci), W, H, 3.0)
     vis = spl["status"] == 2
     return np.where(vis, -spl["view"][:, 2], np.float32(0)).astype(np.float32), vis
 
 
-@pytest.mark.parametrize("W,H,ci", CASES)
-def test_depth_is_the_feature_of_view_z(gpu, orc, torch, c1, scene1, W, H, ci):
+@pytest.mark.parametrize("W,H,ci", CASES + WIDE_CASES)
+def test_depth_is_the_feature_of_view_z(gpu, orc, torch, scene_of, W, H, ci):
     """The depth plane equals the feature plane of zf = -view z (the oracle's, 0 for
     culled Gaussians) bit for bit: the stored value is the oracle's float, composited like
     any other channel.  Where alpha >= 0.5 the expected depth lies within the visible
     splats' range, widened by 2^-20 relative (far above the fma chain's rounding, a few
     hundred takes x 2^-24: the bound only catches gross errors)."""
-    cam = cam_for(gpu, W, H, **CAMS[ci])
+    c1, scene1 = scene_of(ci)
+    cam = cam_of(gpu, W, H, ci)
     zf, vis = depth_values(orc, gpu, c1, W, H, ci)
     d = aux(gpu, torch, scene1, cam, W, H, out=False, alpha=False)["depth"]
     f = aux(gpu, torch, scene1, cam, W, H, out=False, alpha=False, depth=False, feats=zf[None])["feat"][0]

@@ -55,6 +55,15 @@ def dense(gpu):
     return soa, gpu.Scene.from_soa(soa)
 
 
+@pytest.fixture(scope="module")
+def tilted(gpu):
+    """_wide_scenes' tilted scene: random quaternions (the dense scene's is the identity), so
+    the conics carry off-diagonal terms of their own and the ellipses cross blocks at an angle."""
+    from _wide_scenes import scene as wide_scene
+    soa = wide_scene("tilted")
+    return soa, gpu.Scene.from_soa(soa)
+
+
 # ---------------------------------------------------------------- the reference
 
 def marked_soa(soa, ids):
@@ -98,10 +107,10 @@ def plane_stats(w):
 _dense_refs = {}
 
 
-def dense_ref(orc, gsr, soa, W, H, tiling=None):
-    """All 200 planes of the dense scene (67 oracle renders), once per (size, tiling):
-    {"P": (n, H, W), "count", "weight", "max": (n,), "id": (H, W)}."""
-    key = (W, H, tiling)
+def dense_ref(orc, gsr, soa, W, H, tiling=None, name="dense"):
+    """All 200 planes of the dense (or tilted) scene (67 oracle renders), once per (scene, size,
+    tiling): {"P": (n, H, W), "count", "weight", "max": (n,), "id": (H, W)}."""
+    key = (name, W, H, tiling)
     if key not in _dense_refs:
         n = soa.shape[1]
         cam = cam_for(gsr, W, H)
@@ -194,30 +203,32 @@ def assert_contrib_equal(got, ref, keys=("count", "weight", "max", "id")):
 
 # ---------------------------------------------------------------- 1. dense scene, every Gaussian
 
-def test_dense_scene_every_gaussian_exact(gpu, orc, torch, dense):
-    """96 x 64, 200 Gaussians: all four outputs equal the oracle's planes exactly.  The
-    reference is first shown to hold what makes the comparison meaningful: lists longer than
-    one batch, saturated pixels, no ties, and dominant splats that are not the nearest."""
-    soa, scene = dense
-    W, H = 96, 64
+@pytest.mark.parametrize("name,W,H", [("dense", 96, 64), ("tilted", 128, 80)])
+def test_dense_scene_every_gaussian_exact(gpu, orc, torch, request, name, W, H):
+    """96 x 64, 200 Gaussians (and the tilted scene's 200 at 128 x 80): all four outputs equal
+    the oracle's planes exactly.  The reference is first shown to hold what makes the
+    comparison meaningful: lists longer than one batch and no ties; for the dense scene also
+    saturated pixels and dominant splats that are not the nearest."""
+    soa, scene = request.getfixturevalue(name)
     cam = cam_for(gpu, W, H)
-    ref = dense_ref(orc, gpu, soa, W, H)
+    ref = dense_ref(orc, gpu, soa, W, H, name=name)
     P = ref["P"]
     takes = (P != 0).sum(0)
     print("max takes per pixel", int(takes.max()))
     assert takes.max() > 64
-    alpha = orc.render(ones_soa(soa), cam, W, H, 3.0)[0]
-    print("saturated pixels", int((alpha >= 0.999).sum()))
-    assert (alpha >= 0.999).sum() >= 500
     ties = ((P == P.max(0)) & (P.max(0) > 0)).sum(0) > 1
     print("ties", int(ties.sum()))
     assert ties.sum() == 0
     spl = orc.preprocess(soa, cam, W, H, 3.0)
-    order = (orc.expected_depth_order(spl) & np.uint64(0xFFFFFFFF)).astype(np.int64)
-    nearest = order[(P[order] != 0).argmax(0)]
-    dom_not_near = (takes > 0) & (ref["id"] != nearest)
-    print("dominant != nearest", int(dom_not_near.sum()))
-    assert dom_not_near.sum() >= 1000
+    if name == "dense":     # what this scene was built for
+        alpha = orc.render(ones_soa(soa), cam, W, H, 3.0)[0]
+        print("saturated pixels", int((alpha >= 0.999).sum()))
+        assert (alpha >= 0.999).sum() >= 500
+        order = (orc.expected_depth_order(spl) & np.uint64(0xFFFFFFFF)).astype(np.int64)
+        nearest = order[(P[order] != 0).argmax(0)]
+        dom_not_near = (takes > 0) & (ref["id"] != nearest)
+        print("dominant != nearest", int(dom_not_near.sum()))
+        assert dom_not_near.sum() >= 1000
     hidden = (spl["status"] == 2) & (ref["count"] == 0)
     print("visible but never composited", int(hidden.sum()))
     # the take map agrees with the planes (count and index hash per pixel)

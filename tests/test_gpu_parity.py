@@ -133,18 +133,17 @@ CAMS = [dict(pos=(0, 0, 4)), dict(pos=(1.0, 0.5, 3.0), look=(0.2, 0, 0), fov=70)
         dict(pos=(-2.5, -1.0, -3.0))]
 
 
-@pytest.mark.parametrize("ci", range(len(CAMS)))
-def test_preprocess_records_bit_exact(gpu, orc, torch, c1, ci):
-    path, soa = c1
-    W, H = 640, 480
-    cam = cam_for(gpu, W, H, **CAMS[ci])
+def check_preprocess_records(gpu, orc, soa, cam, W, H, k=3.0, pairs_of=rect_pairs):
+    """The records, the depth order, tile_count, the pair list and the tile ranges of one frame
+    without tile row spans, bit for bit against the oracle's records.  pairs_of: rect_pairs,
+    or a faster statement of it for scenes of many pairs."""
     scene = gpu.Scene.from_soa(soa)
     r = gpu.Renderer()
     r.set_tuning(KNOB_TILE_SPANS, 0)   # every tile of every rect (the spans test covers 1)
-    r.preprocess(scene, cam, W, H, k=3.0)
+    r.preprocess(scene, cam, W, H, k=k)
     r.sort()
     got = r.read_splats(soa.shape[1])
-    want = orc.preprocess(soa, cam, W, H, 3.0)
+    want = orc.preprocess(soa, cam, W, H, k)
     vis = want["status"] == 2
     assert vis.sum() > 0
     assert np.array_equal(got["tile_count"][~vis], np.zeros((~vis).sum(), np.uint32))
@@ -167,7 +166,7 @@ def test_preprocess_records_bit_exact(gpu, orc, torch, c1, ci):
     order = r.read_depth_order(soa.shape[1])
     assert np.array_equal(order, orc.expected_depth_order(want))
 
-    ex_pairs = rect_pairs(want, order, W, H)
+    ex_pairs = pairs_of(want, order, W, H)
     pairs = r.read_pairs()
     assert r.pair_count() == ex_pairs.size
     assert np.array_equal(pairs, ex_pairs)
@@ -177,6 +176,51 @@ def test_preprocess_records_bit_exact(gpu, orc, torch, c1, ci):
     nz = counts > 0
     assert np.array_equal((ranges[nz, 1] - ranges[nz, 0]).astype(np.int64), counts[nz])
     assert (ranges[~nz, 1] == ranges[~nz, 0]).all()
+    return want
+
+
+@pytest.mark.parametrize("ci", range(len(CAMS)))
+def test_preprocess_records_bit_exact(gpu, orc, torch, c1, ci):
+    path, soa = c1
+    W, H = 640, 480
+    check_preprocess_records(gpu, orc, soa, cam_for(gpu, W, H, **CAMS[ci]), W, H)
+
+
+def check_tile_spans(gpu, orc, torch, soa, cam, W, H, k=3.0, floor=0.05, pairs_of=rect_pairs):
+    """Tile row spans on against off over one frame (test_tile_spans_drop_only_unreachable_pairs).
+    floor: the dropped share of the rect pairs must exceed it, so that spans that do nothing
+    cannot pass.  Returns (rect pairs, dropped pairs, largest alpha of a dropped pair)."""
+    scene = gpu.Scene.from_soa(soa)
+    # exact blend: the lists differ, so the fast blend's guard band (which counts list
+    # entries) could re-blend different blocks; the exact images must be identical
+    r_on, r_off = exact_blend(gpu.Renderer()), exact_blend(gpu.Renderer())
+    assert r_on.get_tuning(KNOB_TILE_SPANS) == 2   # default: on up to 1.5M Gaussians
+    r_on.set_tuning(KNOB_TILE_SPANS, 1)
+    r_off.set_tuning(KNOB_TILE_SPANS, 0)
+    with pytest.raises(gpu.GsrError):
+        r_off.set_tuning(KNOB_TILE_SPANS, 3)
+    got_on, _ = render_gpu(gpu, torch, scene, cam, W, H, k=k, renderer=r_on)
+    got_off, _ = render_gpu(gpu, torch, scene, cam, W, H, k=k, renderer=r_off)
+    assert np.array_equal(got_on.view(np.uint32), got_off.view(np.uint32))
+    assert_image_parity(got_on, orc.render(soa, cam, W, H, k), exact=True)
+    want = orc.preprocess(soa, cam, W, H, k)
+    full = pairs_of(want, r_on.read_depth_order(soa.shape[1]), W, H)
+    assert np.array_equal(r_off.read_pairs(), full)
+    on = r_on.read_pairs()
+    assert r_on.pair_count() == full.size          # pair_count: every tile of every rect
+    kept = np.isin(full, on)
+    assert np.array_equal(on, full[kept])          # a subsequence: same order, nothing new
+    dropped = full[~kept]
+    peak = max_alpha_on_tiles(want, dropped, W)
+    print(f"rect pairs {full.size}, dropped {dropped.size} ({dropped.size / max(full.size, 1):.4f}), "
+          f"largest alpha of a dropped pair {float(peak.max(initial=0.0)):.4e}")
+    assert dropped.size > floor * full.size
+    assert (peak < np.float32(1e-3)).all()
+    # the row pass still makes one item per covered tile row
+    spl = r_on.read_splats(soa.shape[1])
+    ty = spl["tile_y_range"][spl["tile_count"] > 0]
+    assert r_on.row_item_count() == int(((ty >> 16) - (ty & 0xFFFF) + 1).sum())
+    return full.size, dropped.size, float(peak.max(initial=0.0))
 
 
 @pytest.mark.parametrize("ci", range(len(CAMS)))
@@ -187,34 +231,7 @@ def test_tile_spans_drop_only_unreachable_pairs(gpu, orc, torch, c1, ci):
     bit-identical to the one without spans and to the oracle's."""
     path, soa = c1
     W, H = 640, 480
-    cam = cam_for(gpu, W, H, **CAMS[ci])
-    scene = gpu.Scene.from_soa(soa)
-    # exact blend: the lists differ, so the fast blend's guard band (which counts list
-    # entries) could re-blend different blocks; the exact images must be identical
-    r_on, r_off = exact_blend(gpu.Renderer()), exact_blend(gpu.Renderer())
-    assert r_on.get_tuning(KNOB_TILE_SPANS) == 2   # default: on up to 1.5M Gaussians
-    r_on.set_tuning(KNOB_TILE_SPANS, 1)
-    r_off.set_tuning(KNOB_TILE_SPANS, 0)
-    with pytest.raises(gpu.GsrError):
-        r_off.set_tuning(KNOB_TILE_SPANS, 3)
-    got_on, _ = render_gpu(gpu, torch, scene, cam, W, H, renderer=r_on)
-    got_off, _ = render_gpu(gpu, torch, scene, cam, W, H, renderer=r_off)
-    assert np.array_equal(got_on.view(np.uint32), got_off.view(np.uint32))
-    assert_image_parity(got_on, orc.render(soa, cam, W, H, 3.0), exact=True)
-    want = orc.preprocess(soa, cam, W, H, 3.0)
-    full = rect_pairs(want, r_on.read_depth_order(soa.shape[1]), W, H)
-    assert np.array_equal(r_off.read_pairs(), full)
-    on = r_on.read_pairs()
-    assert r_on.pair_count() == full.size          # pair_count: every tile of every rect
-    kept = np.isin(full, on)
-    assert np.array_equal(on, full[kept])          # a subsequence: same order, nothing new
-    dropped = full[~kept]
-    assert dropped.size > 0.05 * full.size         # ~24 % on config 2
-    assert (max_alpha_on_tiles(want, dropped, W) < np.float32(1e-3)).all()
-    # the row pass still makes one item per covered tile row
-    spl = r_on.read_splats(soa.shape[1])
-    ty = spl["tile_y_range"][spl["tile_count"] > 0]
-    assert r_on.row_item_count() == int(((ty >> 16) - (ty & 0xFFFF) + 1).sum())
+    check_tile_spans(gpu, orc, torch, soa, cam_for(gpu, W, H, **CAMS[ci]), W, H)   # ~24 % dropped on config 2
 
 
 @pytest.mark.parametrize("ci", range(len(CAMS)))
@@ -252,19 +269,14 @@ def test_blend_block_mappings_parity(gpu, orc, torch, c1, knobs):
             r.set_blend_variant(v)
 
 
-@pytest.mark.parametrize("knobs", [{}, {8: 4, 9: 16}, {8: 16, 9: 4, 10: 7}, {31: 2048}, {31: 2048, 10: 7},
-                                   {31: 1024, 9: 16, 10: 7}])
-def test_tile_binning_matches_pair_sort(gpu, orc, torch, c1, knobs):
-    """Row + column binning (default for grids <= 256 x 256 tiles) gives the same
-    tile lists as pair emission + the key-value tile sort: identical (tile,
-    Gaussian) pairs in identical order, identical images, both equal to the
-    oracle.  Knobs 8/9: items per thread of the row / column tiles (4, 16);
-    10: column-pass workgroups (7 forces the grid-stride chunk loop); 31: row items
-    per column-pass chunk (1024, the default at this size, or 2048)."""
-    path, soa = c1
-    W, H = 1000, 700
+BINNING_KNOBS = [{}, {8: 4, 9: 16}, {8: 16, 9: 4, 10: 7}, {31: 2048}, {31: 2048, 10: 7}, {31: 1024, 9: 16, 10: 7}]
+
+
+def check_binning_matches_pair_sort(gpu, orc, torch, soa, cam, W, H, knobs, min_pairs=10_000):
+    """One frame through the row + column binning with the given knobs and through the pair
+    sort (knob 7 = 0), tile row spans off: the same pairs in the same order, the same image,
+    the oracle's image (test_tile_binning_matches_pair_sort)."""
     scene = gpu.Scene.from_soa(soa)
-    cam = cam_for(gpu, W, H, pos=(0.4, 0.3, 3.5))
     r_bin, r_sort = exact_blend(gpu.Renderer()), exact_blend(gpu.Renderer())
     for kn, v in knobs.items():
         r_bin.set_tuning(kn, v)
@@ -274,7 +286,7 @@ def test_tile_binning_matches_pair_sort(gpu, orc, torch, c1, knobs):
     got_sort, _ = render_gpu(gpu, torch, scene, cam, W, H, renderer=r_sort)
     assert np.array_equal(got_bin.view(np.uint32), got_sort.view(np.uint32))
     pb, ps = r_bin.read_pairs(), r_sort.read_pairs()
-    assert pb.shape == ps.shape and pb.shape[0] > 10_000
+    assert pb.shape == ps.shape and pb.shape[0] > min_pairs
     assert np.array_equal(pb, ps)
     assert_image_parity(got_bin, orc.render(soa, cam, W, H, 3.0), exact=True)
     # the row pass made one item per covered tile row of every visible splat
@@ -283,6 +295,20 @@ def test_tile_binning_matches_pair_sort(gpu, orc, torch, c1, knobs):
     ty = spl["tile_y_range"][live]
     assert r_bin.row_item_count() == int(((ty >> 16) - (ty & 0xFFFF) + 1).sum())
     assert r_sort.row_item_count() == -1
+    return pb
+
+
+@pytest.mark.parametrize("knobs", BINNING_KNOBS)
+def test_tile_binning_matches_pair_sort(gpu, orc, torch, c1, knobs):
+    """Row + column binning (default for grids <= 256 x 256 tiles) gives the same
+    tile lists as pair emission + the key-value tile sort: identical (tile,
+    Gaussian) pairs in identical order, identical images, both equal to the
+    oracle.  Knobs 8/9: items per thread of the row / column tiles (4, 16);
+    10: column-pass workgroups (7 forces the grid-stride chunk loop); 31: row items
+    per column-pass chunk (1024, the default at this size, or 2048)."""
+    path, soa = c1
+    W, H = 1000, 700
+    check_binning_matches_pair_sort(gpu, orc, torch, soa, cam_for(gpu, W, H, pos=(0.4, 0.3, 3.5)), W, H, knobs)
 
 
 def test_tile_binning_8bit_digits(gpu, orc, torch, c1):

@@ -2,12 +2,14 @@
 tile_row_spans (gsr_kernels.hip) on the oracle's preprocess records.  For each scene it
 prints the fraction of (tile, splat) rect pairs the spans keep and the largest alpha any
 DROPPED pair reaches on an in-box pixel of its tile (must stay < 1e-3: the drop is then
-invisible).  `python tools/sim/spans_check.py c1` (config 1, four cameras) or `c2`
-(config 2; needs /tmp/sim_1000000.ply from tools/sim/sim_blend.py)."""
-import os, sys, numpy as np
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+invisible).  `python tools/sim/spans_check.py c1` (config 1, four cameras), `c2` (config
+2) or `wide` (the scenes of tests/_wide_scenes.py that tests/test_gpu_wide.py runs the spans
+on: large, tilted and clipped splats, centres far off screen)."""
+import os, sys, tempfile, numpy as np
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import gaussianrenderer_amd as gsr, _oracle as orc
-from test_gpu_parity import rect_pairs, max_alpha_on_tiles, CAMS, cam_for
+from test_gpu_parity import max_alpha_on_tiles, CAMS, cam_for
 f32 = np.float32
 def spans_np(want, W, H):
     v = want["status"] == 2
@@ -65,26 +67,37 @@ def listed(full, code, tx0, tx1, ty0, W):
     sp = np.where(ro < 4, (code[idx] >> (4 * np.minimum(ro, 3)).astype(np.uint32)) & 0xf, 0)
     c0 = tx0[idx] + (sp & 3); c1 = tx1[idx] - (sp >> 2)
     return (col >= c0) & (col <= c1)
-cfg = sys.argv[1]
-if cfg == "c1":
-    p = "/tmp/c1.ply"; soa = gsr.read_ply(p); W, H = 640, 480; cams = [cam_for(gsr, W, H, **kw) for kw in CAMS]
-else:
-    p = "/tmp/sim_1000000.ply"; soa = gsr.read_ply(p); W, H = 1920, 1080; cams = [gsr.make_camera(position=(0, 0, 4), fov_y=50, aspect=W / H)]
-for cam in cams:
-    want = orc.preprocess(soa, cam, W, H, 3.0)
-    order = orc.expected_depth_order(want)
-    full = rect_pairs(want, order, W, H) if cfg == "c1" else None
-    if full is None:
-        # vectorized rect pairs for the big scene (order irrelevant here)
-        vis = np.nonzero(want["status"] == 2)[0]; a = want["aabb"][vis].astype(np.int64)
-        tx, ty = (W + 15) // 16, (H + 15) // 16
-        x0 = a[:, 0] // 16; x1 = np.minimum(tx - 1, a[:, 2] // 16); y0 = a[:, 1] // 16; y1 = np.minimum(ty - 1, a[:, 3] // 16)
-        cnt = (x1 - x0 + 1) * (y1 - y0 + 1); rep = np.repeat(np.arange(len(vis)), cnt); st = np.repeat(np.cumsum(cnt) - cnt, cnt)
-        kk = np.arange(rep.size) - st; ww = (x1 - x0 + 1)[rep]
-        tile = (y0[rep] + kk // ww) * tx + x0[rep] + kk % ww
-        full = (tile.astype(np.uint64) << np.uint64(32)) | vis[rep].astype(np.uint64)
+def synthetic(n, seed):
+    with tempfile.TemporaryDirectory() as d:
+        p = os.path.join(d, "s.ply"); gsr.write_synthetic_ply(p, n, seed)
+        return gsr.read_ply(p)
+def report(label, soa, cam, W, H, k=3.0):
+    from _wide_scenes import rect_pairs as fast_pairs
+    want = orc.preprocess(soa, cam, W, H, k)
+    full = fast_pairs(want, orc.expected_depth_order(want), W, H)
     code, tx0, tx1, ty0 = spans_np(want, W, H)
     keep = listed(full, code, tx0, tx1, ty0, W)
     dropped = full[~keep]
     al = max_alpha_on_tiles(want, dropped, W)
-    print(f"pairs {full.size} kept {keep.mean():.3f} dropped {dropped.size} max alpha of dropped {al.max() if al.size else 0:.3e}", flush=True)
+    print(f"{label}: pairs {full.size} kept {keep.mean():.3f} dropped {dropped.size} ({1 - keep.mean():.3f}) max alpha of dropped {al.max() if al.size else 0:.3e}", flush=True)
+cfg = sys.argv[1] if len(sys.argv) > 1 else "c1"
+if cfg == "c1":
+    W, H = 640, 480; soa = synthetic(10_000, 1)
+    for ci, kw in enumerate(CAMS):
+        report(f"config 1 camera {ci}", soa, cam_for(gsr, W, H, **kw), W, H)
+elif cfg == "c2":
+    W, H = 1920, 1080
+    report("config 2", synthetic(1_000_000, 2), gsr.make_camera(position=(0, 0, 4), fov_y=50, aspect=W / H), W, H)
+elif cfg == "wide":
+    import _wide_scenes as ws
+    W, H = ws.W, ws.H
+    for name in ("slabs", "needles", "stack", "huge"):
+        for ci, kw in enumerate(CAMS):
+            report(f"{name} camera {ci} k 3", ws.scene(name), cam_for(gsr, W, H, **kw), W, H)
+    for k in (8.0, 1.0):
+        for ci in (0, 2):
+            report(f"slabs camera {ci} k {k:g}", ws.scene("slabs"), cam_for(gsr, W, H, **CAMS[ci]), W, H, k)
+    for seed in ws.GRAZE_SEEDS:
+        report(f"graze seed {seed}", ws.graze(seed), cam_for(gsr, W, H), W, H)
+else:
+    sys.exit("usage: spans_check.py c1 | c2 | wide")
