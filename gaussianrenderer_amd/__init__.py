@@ -24,6 +24,7 @@ from . import _native
 from ._native import (AUX_MAX_FEATURES, AuxTargets, BackwardTargets, CONTRIB_WEIGHT_ONE, Camera, ContribTargets, GsrError, LAYOUT_AOS, LAYOUT_SCENE_BLOCK, LAYOUT_SCENE_BLOCK_4D,
                       LAYOUT_SCENE_BLOCK_SH3, NUM_STAGES, PLY_SH3, PLY_TYPED, SCENE4D_NARRAYS, SCENE_NARRAYS,
                       SCENE_SH3_NARRAYS, RecordGrads, SceneGrads,
+                      ADAM_OPACITY_MAX, ADAM_OPACITY_MIN, ADAM_SKIP_ZERO, ADAM_ZERO_GRADS, AdamConfig,
                       SPLAT_RECORD_BYTES, STAGES, TILE_PX, check, lib)
 
 __all__ = [
@@ -32,6 +33,7 @@ __all__ = [
     "SPLAT_DTYPE", "STAGES", "TILE_PX", "lib", "AUX_MAX_FEATURES", "DisplayTarget", "display_gl_current", "preprocessCUDAGaussiansGL",
     "CONTRIB_WEIGHT_ONE", "ContribTargets", "BackwardTargets", "mask_indices", "gather_planes",
     "RecordGrads", "SceneGrads",
+    "AdamConfig", "ADAM_SKIP_ZERO", "ADAM_ZERO_GRADS", "ADAM_OPACITY_MIN", "ADAM_OPACITY_MAX", "SCENE_GRAD_GROUPS",
 ]
 
 # gsr_read_splats record (include/gsr.h).
@@ -193,6 +195,43 @@ class Scene:
             raise GsrError(_native.GSR_E_ARG, "gsr_scene_gather")
         return Scene(ptr, int(m), narrays=self.narrays)
 
+    def adam_step(self, grads, m, v, *, step: int, lr_position: float = 0.0, lr_opacity: float = 0.0,
+                  lr_scale: float = 0.0, lr_rot: float = 0.0, lr_sh_dc: float = 0.0, lr_sh_rest: float = 0.0,
+                  lr_tcenter: float = 0.0, lr_tscale: float = 0.0, lr_motion: float = 0.0, beta1: float = 0.9,
+                  beta2: float = 0.999, eps: float = 1e-15, skip_zero: bool = False, zero_grads: bool = False,
+                  bad_ptr=None, stream: int = 0) -> None:
+        """One fused in-place Adam step of this block on the device (gsr_scene_adam_step,
+        include/gsr.h), stream-ordered: the one call that writes to a scene block.  grads (what
+        project_backward / render_backward_scene accumulated), m and v (the moments: same
+        shapes, float32 planar [c*n + i], zeroed once by the caller) each name up to six device
+        buffers: a dict with keys from SCENE_GRAD_GROUPS ("position" 3 planes, "opacity" 1,
+        "scale" 3, "rot" 4, "sh" 27 or 48, "temporal" 11; a missing key is None), a sequence of
+        six in that order, or a SceneGrads; every pointer an int, anything with .data_ptr(), or
+        None.  A group is stepped when its gradient is given and its lr is not 0 (lr_sh_dc:
+        the first 3 sh planes, lr_sh_rest: the others; lr_tcenter, lr_tscale, lr_motion: plane
+        0, plane 1, planes 2..10 of "temporal"); a frozen group is neither read nor written.
+        The opacity, the scales and trbf_scale are stepped in raw (logit / log) space.  step:
+        the 1-based iteration, for the bias correction.  skip_zero: elements with a zero
+        gradient keep x, m and v (the visible-only step); zero_grads: the active gradient planes
+        are zero afterwards.  Elements with a non-finite gradient are skipped and counted into
+        the device uint32 bad_ptr (optional; zero it first)."""
+        gs, ms, vs = (_scene_grads(p, name) for p, name in ((grads, "grads"), (m, "m"), (v, "v")))
+        lrs = (lr_position, lr_opacity, lr_scale, lr_rot, lr_sh_dc, lr_sh_rest, lr_tcenter, lr_tscale, lr_motion)
+        active = False
+        for (field, _), glrs in zip(SceneGrads._fields_, (lrs[0:1], lrs[1:2], lrs[2:3], lrs[3:4], lrs[4:6], lrs[6:9])):
+            if getattr(gs, field) and any(lr != 0 for lr in glrs):
+                active = True
+                if not (getattr(ms, field) and getattr(vs, field)):
+                    raise ValueError(f"Scene.adam_step: {field} is stepped but its m or v pointer is missing")
+        if not active:
+            raise ValueError("Scene.adam_step: no group to step (a gradient pointer with a non-zero lr)")
+        if not self.ptr and self.n > 0:
+            raise ValueError("Scene.adam_step: the scene has been freed")
+        cfg = _native.AdamConfig(*[float(lr) for lr in lrs], float(beta1), float(beta2), float(eps), int(step),
+                                 (ADAM_SKIP_ZERO if skip_zero else 0) | (ADAM_ZERO_GRADS if zero_grads else 0))
+        check(lib().gsr_scene_adam_step(self.ptr or None, self.layout, self.n, byref(gs), byref(ms), byref(vs),
+                                        byref(cfg), _dev_ptr(bad_ptr) or None, stream or None), "gsr_scene_adam_step")
+
     def free(self):
         if self.ptr and self.owned:
             lib().gsr_scene_free(self.ptr)
@@ -210,6 +249,29 @@ def _dev_ptr(p) -> int:
     if p is None:
         return 0
     return int(p.data_ptr()) if hasattr(p, "data_ptr") else int(p)
+
+
+# the pointers of a SceneGrads, in the block's array order
+SCENE_GRAD_GROUPS = ("position", "opacity", "scale", "rot", "sh", "temporal")
+
+
+def _scene_grads(p, what: str) -> SceneGrads:
+    """A SceneGrads from a SceneGrads, a dict keyed by SCENE_GRAD_GROUPS or a sequence of six
+    pointers (ints, anything with .data_ptr(), or None)."""
+    if isinstance(p, SceneGrads):
+        return p
+    if p is None:
+        raise ValueError(f"Scene.adam_step: {what} is missing")
+    if isinstance(p, dict):
+        unknown = set(p) - set(SCENE_GRAD_GROUPS)
+        if unknown:
+            raise ValueError(f"Scene.adam_step: {what} has unknown groups {sorted(unknown)}")
+        vals = [p.get(k) for k in SCENE_GRAD_GROUPS]
+    else:
+        vals = list(p)
+        if len(vals) != len(SCENE_GRAD_GROUPS):
+            raise ValueError(f"Scene.adam_step: {what} needs {len(SCENE_GRAD_GROUPS)} pointers ({SCENE_GRAD_GROUPS})")
+    return SceneGrads(*[_dev_ptr(x) or None for x in vals])
 
 
 def mask_indices(keep_ptr, n: int, indices_ptr, stream: int = 0) -> int:

@@ -153,6 +153,25 @@ class SceneGrads(ctypes.Structure):
     ]
 
 
+ADAM_SKIP_ZERO = 1    # gsr_adam_config flags (include/gsr.h)
+ADAM_ZERO_GRADS = 2
+ADAM_OPACITY_MIN = 1e-6        # GSR_ADAM_OPACITY_MIN / MAX, as float32 values
+ADAM_OPACITY_MAX = 0.999999
+
+
+class AdamConfig(ctypes.Structure):
+    """``gsr_adam_config`` (include/gsr.h): learning rates per group, betas, eps, step, flags."""
+
+    _fields_ = [
+        ("lr_position", c_float), ("lr_opacity", c_float), ("lr_scale", c_float), ("lr_rot", c_float),
+        ("lr_sh_dc", c_float), ("lr_sh_rest", c_float),
+        ("lr_tcenter", c_float), ("lr_tscale", c_float), ("lr_motion", c_float),
+        ("beta1", c_float), ("beta2", c_float), ("eps", c_float),
+        ("step", c_int64),
+        ("flags", c_int),
+    ]
+
+
 # (name, restype, argtypes) for every symbol of include/gsr.h and include/gsr_gl.h.
 SIGNATURES = [
     ("preprocessCUDAGaussians", None,
@@ -235,6 +254,9 @@ SIGNATURES = [
                                   c_void_p, c_void_p]),
     ("gsr_scene_gather", c_void_p, [c_void_p, c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     ("gsr_scene_select", c_void_p, [c_void_p, c_int, c_int64, c_void_p, POINTER(c_int64), c_void_p, c_void_p]),
+    # scene optimisation (include/gsr.h)
+    ("gsr_scene_adam_step", c_int, [c_void_p, c_int, c_int64, POINTER(SceneGrads), POINTER(SceneGrads),
+                                    POINTER(SceneGrads), POINTER(AdamConfig), c_void_p, c_void_p]),
     ("gsr_ply_read_host", c_int, [c_char_p, c_void_p, c_int64, POINTER(c_int64)]),
     ("gsr_ply_read_host_ex", c_int, [c_char_p, c_void_p, c_int, c_int64, POINTER(c_int64), c_int, POINTER(c_int)]),
     ("gsr_synth_write_ply", c_int, [c_char_p, c_int64, c_uint64]),

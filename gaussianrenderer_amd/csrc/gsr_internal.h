@@ -1,6 +1,6 @@
 // gsr_internal.h — shared between the host runtime (gsr_runtime.cpp) and the
 // gfx950 kernels (gsr_kernels.hip, gsr_blend.hip, gsr_blend_derived.hip, gsr_scene_ops.hip,
-// gsr_project.hip, gsr_probes.hip).  Not part of the public ABI.
+// gsr_scene_adam.hip, gsr_project.hip, gsr_probes.hip).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -312,6 +312,29 @@ hipError_t launch_mask_indices(const uint8_t* keep, uint32_t n, uint32_t* counts
 hipError_t launch_gather_planes(void* dst, int64_t dst_stride, const void* src, int64_t src_stride, int nplanes,
                                 int elem_bytes, uint32_t n, const int32_t* idx, uint32_t m, uint32_t* bad,
                                 void* scene_header, hipStream_t s);
+
+// Scene optimisation (gsr_scene_adam_step; k_scene_adam, gsr_scene_adam.hip): one launch steps
+// every active plane.  The plane table travels in the kernel arguments (the call never
+// allocates): per active plane the block array it steps, its gradient and moment planes, its
+// learning rate and how the stored value is stepped.  flags: GSR_ADAM_*; the host has
+// checked every argument (gsr_runtime.cpp).  n == 0 or no plane launches nothing.
+enum { kAdamPlain = 0, kAdamExp = 1, kAdamOpacity = 2 };   // x - d | x exp(-d) | the logit step
+struct AdamPlane {
+    float* g;
+    float* m;
+    float* v;
+    float lr;
+    uint16_t array;   // index of the block array
+    uint16_t kind;    // kAdam*
+};
+struct AdamLaunch {
+    AdamPlane plane[GSR_SCENE_SH3_NARRAYS];   // the largest block kind
+    int nplanes;
+    float beta1, beta2, omb1, omb2, bc1, bc2, eps;
+    int flags;
+};
+hipError_t launch_scene_adam(float* arrays, int64_t stride, uint32_t n, const AdamLaunch& L, uint32_t* bad,
+                             hipStream_t s);
 
 // Device self-check of the lane order of same-address returning LDS atomics (the
 // RA rank path): runs k_rank_order_check synchronously on the current device and

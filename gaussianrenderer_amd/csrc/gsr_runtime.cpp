@@ -385,6 +385,81 @@ extern "C" void* gsr_scene_select(const void* d_scene, int narrays, int64_t n, c
     return d;
 }
 
+// ---- scene optimisation (kernel: gsr_scene_adam.hip) ----
+
+extern "C" int gsr_scene_adam_step(void* d_scene, int layout, int64_t n, const gsr_scene_grads* grads,
+                                   const gsr_scene_grads* m, const gsr_scene_grads* v, const gsr_adam_config* cfg,
+                                   uint32_t* d_bad, void* stream) {
+    const char* who = "gsr_scene_adam_step";
+    if (!grads || !m || !v || !cfg) return set_err(GSR_E_ARG, "%s: null grads, m, v or cfg", who);
+    if (layout != GSR_LAYOUT_SCENE_BLOCK && layout != GSR_LAYOUT_SCENE_BLOCK_4D && layout != GSR_LAYOUT_SCENE_BLOCK_SH3)
+        return set_err(GSR_E_ARG, "%s: layout %d is not a scene block", who, layout);
+    if (n < 0 || n > INT32_MAX) return set_err(GSR_E_ARG, "%s: n = %lld out of range", who, (long long)n);
+    if (n > 0 && !d_scene) return set_err(GSR_E_ARG, "%s: null scene", who);
+    const float lrs[9] = {cfg->lr_position, cfg->lr_opacity, cfg->lr_scale, cfg->lr_rot, cfg->lr_sh_dc,
+                          cfg->lr_sh_rest, cfg->lr_tcenter, cfg->lr_tscale, cfg->lr_motion};
+    for (float lr : lrs)
+        if (!std::isfinite(lr) || lr < 0.0f) return set_err(GSR_E_ARG, "%s: a learning rate is negative or not finite", who);
+    if (!(cfg->beta1 >= 0.0f && cfg->beta1 < 1.0f) || !(cfg->beta2 >= 0.0f && cfg->beta2 < 1.0f))
+        return set_err(GSR_E_ARG, "%s: beta1 = %g, beta2 = %g outside [0, 1)", who, cfg->beta1, cfg->beta2);
+    if (!std::isfinite(cfg->eps) || !(cfg->eps > 0.0f)) return set_err(GSR_E_ARG, "%s: eps = %g", who, cfg->eps);
+    if (cfg->step < 1) return set_err(GSR_E_ARG, "%s: step = %lld < 1", who, (long long)cfg->step);
+    if (cfg->flags & ~(GSR_ADAM_SKIP_ZERO | GSR_ADAM_ZERO_GRADS))
+        return set_err(GSR_E_ARG, "%s: unknown flag bits 0x%x", who, cfg->flags);
+
+    // the groups in the block's array order: {gradient, moments, first plane of the pointer,
+    // planes, first block array, lr, update kind}
+    const bool four_d = layout == GSR_LAYOUT_SCENE_BLOCK_4D;
+    const int sh_rest = layout == GSR_LAYOUT_SCENE_BLOCK_SH3 ? GSR_SCENE_SH3_NARRAYS - GSR_A_SH0 - 3
+                                                             : GSR_SCENE_NARRAYS - GSR_A_SH0 - 3;
+    struct Group {
+        float *g, *m, *v;
+        int first, planes, array;
+        float lr;
+        int kind;
+        bool temporal;
+    };
+    const Group groups[9] = {
+        {grads->d_position, m->d_position, v->d_position, 0, 3, GSR_A_X, cfg->lr_position, gsr::kAdamPlain, false},
+        {grads->d_opacity, m->d_opacity, v->d_opacity, 0, 1, GSR_A_OPACITY, cfg->lr_opacity, gsr::kAdamOpacity, false},
+        {grads->d_scale, m->d_scale, v->d_scale, 0, 3, GSR_A_SCALE0, cfg->lr_scale, gsr::kAdamExp, false},
+        {grads->d_rot, m->d_rot, v->d_rot, 0, 4, GSR_A_ROT0, cfg->lr_rot, gsr::kAdamPlain, false},
+        {grads->d_sh, m->d_sh, v->d_sh, 0, 3, GSR_A_SH0, cfg->lr_sh_dc, gsr::kAdamPlain, false},
+        {grads->d_sh, m->d_sh, v->d_sh, 3, sh_rest, GSR_A_SH0 + 3, cfg->lr_sh_rest, gsr::kAdamPlain, false},
+        {grads->d_temporal, m->d_temporal, v->d_temporal, 0, 1, GSR_A_TCENTER, cfg->lr_tcenter, gsr::kAdamPlain, true},
+        {grads->d_temporal, m->d_temporal, v->d_temporal, 1, 1, GSR_A_TSCALE, cfg->lr_tscale, gsr::kAdamExp, true},
+        {grads->d_temporal, m->d_temporal, v->d_temporal, 2, 9, GSR_A_MOTION0, cfg->lr_motion, gsr::kAdamPlain, true},
+    };
+    gsr::AdamLaunch L{};
+    uintptr_t align = reinterpret_cast<uintptr_t>(d_scene) | reinterpret_cast<uintptr_t>(d_bad);
+    for (const Group& gr : groups) {
+        if (!gr.g || gr.lr == 0.0f) continue;   // frozen: neither read nor written
+        if (gr.temporal && !four_d) return set_err(GSR_E_ARG, "%s: d_temporal needs a 4D scene block", who);
+        if (!gr.m || !gr.v) return set_err(GSR_E_ARG, "%s: an active group lacks a moment plane", who);
+        align |= reinterpret_cast<uintptr_t>(gr.g) | reinterpret_cast<uintptr_t>(gr.m) | reinterpret_cast<uintptr_t>(gr.v);
+        for (int p = 0; p < gr.planes; p++) {
+            const int64_t off = (int64_t)(gr.first + p) * n;
+            L.plane[L.nplanes++] = gsr::AdamPlane{gr.g + off, gr.m + off, gr.v + off, gr.lr, (uint16_t)(gr.array + p),
+                                                  (uint16_t)gr.kind};
+        }
+    }
+    if (L.nplanes == 0) return set_err(GSR_E_ARG, "%s: no active group (a gradient pointer with a non-zero lr)", who);
+    if (align % 4) return set_err(GSR_E_ARG, "%s: misaligned pointer", who);
+    if (n == 0) return GSR_OK;
+    const double b1 = (double)cfg->beta1, b2 = (double)cfg->beta2, t = (double)cfg->step;
+    L.beta1 = cfg->beta1;
+    L.beta2 = cfg->beta2;
+    L.omb1 = (float)(1.0 - b1);
+    L.omb2 = (float)(1.0 - b2);
+    L.bc1 = (float)(1.0 - std::pow(b1, t));
+    L.bc2 = (float)(1.0 - std::pow(b2, t));
+    L.eps = cfg->eps;
+    L.flags = cfg->flags;
+    float* arrays = reinterpret_cast<float*>(static_cast<char*>(d_scene) + GSR_SCENE_HEADER_BYTES);
+    HIP_TRY(gsr::launch_scene_adam(arrays, scene_stride(n), (uint32_t)n, L, d_bad, static_cast<hipStream_t>(stream)));
+    return GSR_OK;
+}
+
 extern "C" void* gsr_scene_upload(const float* host_soa, int64_t n) {
     return gsr_scene_upload_ex(host_soa, GSR_SCENE_NARRAYS, n);
 }

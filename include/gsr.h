@@ -707,7 +707,8 @@ int gsr_scene_download(const void* d_scene, float* host_soa, int64_t n);
 
 /* ---- scene editing: new scene blocks from a keep mask or an index list, on the device ----
  *
- * The consumer half of gsr_render_contrib: a scene block is immutable, and these calls build
+ * The consumer half of gsr_render_contrib: a selection never edits a scene block in place (the
+ * one writer of a block is gsr_scene_adam_step, below); these calls build
  * a new one (a pruned scene, a level-of-detail or visibility subset, a reordered scene)
  * without the download / numpy / upload round trip, and cut the caller's per-Gaussian side
  * arrays (gsr_render_aux's feature planes, gsr_render_contrib's accumulators) down in step.
@@ -757,6 +758,81 @@ void* gsr_scene_gather(const void* d_scene, int narrays, int64_t n, const int32_
  * allocated). */
 void* gsr_scene_select(const void* d_scene, int narrays, int64_t n, const uint8_t* d_keep, int64_t* m_out,
                        int32_t* d_indices, void* stream);
+
+/* ---- scene optimisation: the one call that writes to a scene block ----
+ *
+ * The update of render -> loss -> gsr_render_backward_scene -> UPDATE -> prune: one fused,
+ * in-place Adam step of the block's arrays from gsr_project_backward's gradient planes, so a
+ * scene is fine-tuned, or re-fitted after a prune, without leaving the device.  Context-free,
+ * stream-ordered: it never allocates, synchronises or reads the block's header, and trusts
+ * (layout, n) as gsr_render does.
+ *
+ * grads are gsr_project_backward's outputs; m and v, the first and second moments, have the
+ * same shapes (planar [c*n + i], the block's array order), are owned by the caller, zeroed
+ * once, and cut down with the scene by gsr_gather_planes after a prune.
+ *
+ * Groups, each with its own learning rate: d_position (lr_position), d_opacity (lr_opacity),
+ * d_scale (lr_scale), d_rot (lr_rot); d_sh is two groups, its first 3 planes the dc
+ * coefficients (lr_sh_dc) and its other 24 (45 for an SH-3 block) the rest (lr_sh_rest);
+ * d_temporal is three, plane 0 trbf_center (lr_tcenter), plane 1 trbf_scale (lr_tscale),
+ * planes 2..10 the motion arrays (lr_motion).  A group is ACTIVE when its gradient pointer is
+ * non-NULL and its lr is not 0; a frozen group is neither read nor written, and its moment
+ * pointers may be NULL.
+ *
+ * The block stores the opacity as sigmoid(raw) and the scales and trbf_scale as exp(raw); the
+ * gradients are with respect to the stored values.  The step is the 3DGS parametrisation's, in
+ * raw space, written without a log.  Per element, in float32, every operation rounded once
+ * (no FMA), in exactly this order — with omb1 = 1 - beta1, omb2 = 1 - beta2, bc1 = 1 -
+ * pow(beta1, step), bc2 = 1 - pow(beta2, step) computed by the host in double from the float
+ * betas and rounded to float:
+ *   g' = g * chain       chain = 1 for the plain arrays (g' = g),
+ *                        o * (1 - o) for the opacity, s for the scales and trbf_scale
+ *   m' = (beta1 * m) + (omb1 * g')
+ *   v' = (beta2 * v) + ((omb2 * g') * g')
+ *   d  = (lr * (m' / bc1)) / (sqrtf(v' / bc2) + eps)
+ *   position, rot, sh, trbf_center, motion:   x' = x - d
+ *   scale, trbf_scale:                        s' = s * gsr_expf(-d)           (log s - d)
+ *   opacity:   o' = o / (o + (1 - o) * gsr_expf(d))                           (logit o - d)
+ *              then fminf(fmaxf(o', GSR_ADAM_OPACITY_MIN), GSR_ADAM_OPACITY_MAX)
+ * gsr_expf is gsr_detmath.h's.  The quaternion is stepped raw (its gradient already runs
+ * through the normalisation).
+ *
+ * Skipped elements keep their bits in x, m and v:
+ *   - g not finite: skipped, and *d_bad (may be NULL; a device word the caller zeroes) is
+ *     incremented by the number of such elements;
+ *   - with GSR_ADAM_SKIP_ZERO, g = +-0: skipped.  gsr_project_backward never touches a
+ *     Gaussian that no pixel composited, so this is the visible-only ("sparse") Adam: the
+ *     moments of what a batch did not see do not decay.  A wave whose gradients are all zero
+ *     loads nothing else.
+ * With GSR_ADAM_ZERO_GRADS every element of every active group's gradient planes reads +-0
+ * after the call, the skipped ones included: the batch's memset pass is saved.
+ *
+ * One thread owns one element, no atomics but *d_bad: reproducible bit for bit.  Elements
+ * [n, stride) of the block, and everything past n in any plane, are never read or written.
+ * The step is ordered on `stream`: frames of gsr_render_path* still in flight on other lanes
+ * must have joined it first (the default join does; with GSR_PATH_NO_JOIN wait on the frame
+ * events).  A stepped block renders through an existing context like any other frame: no
+ * context state holds scene contents.
+ * GSR_E_ARG, before any device work: d_scene NULL with n > 0; grads, m, v or cfg NULL;
+ * GSR_LAYOUT_AOS or an unknown layout; n outside [0, INT32_MAX]; no active group; an active
+ * group without both moment planes; d_temporal active on a block that is not 4D; an lr that is
+ * negative or not finite; beta1 or beta2 outside [0, 1); eps not finite or <= 0; step < 1;
+ * unknown flag bits; a pointer that is not 4-byte aligned.  n == 0 is GSR_OK without device
+ * work. */
+enum { GSR_ADAM_SKIP_ZERO = 1, GSR_ADAM_ZERO_GRADS = 2 };
+#define GSR_ADAM_OPACITY_MIN 1e-6f
+#define GSR_ADAM_OPACITY_MAX 0.999999f
+typedef struct gsr_adam_config {
+    float lr_position, lr_opacity, lr_scale, lr_rot, lr_sh_dc, lr_sh_rest;   /* 3D groups */
+    float lr_tcenter, lr_tscale, lr_motion;                                  /* 4D blocks only */
+    float beta1, beta2, eps;
+    int64_t step;      /* t >= 1, for the bias correction */
+    int flags;         /* GSR_ADAM_* */
+} gsr_adam_config;
+int gsr_scene_adam_step(void* d_scene, int layout, int64_t n,
+                        const gsr_scene_grads* grads,   /* gsr_project_backward's outputs */
+                        const gsr_scene_grads* m, const gsr_scene_grads* v,   /* moments, same shapes, caller-owned */
+                        const gsr_adam_config* cfg, uint32_t* d_bad, void* stream);
 
 /* ---------------------------------------------------------------- host helpers */
 
