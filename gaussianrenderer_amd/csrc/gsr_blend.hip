@@ -402,15 +402,29 @@ __device__ __forceinline__ uint64_t blend_block(const uint32_t* __restrict__ idx
                     take1 = in1 & !(TT.y < 1e-3f) & pass1;
                 }
                 AA.y = take1 ? al1 : 0.0f;
-                // the three colour products, then rgb += (col * alpha) * T as fused
-                // multiply-adds in list order (render.cu:337, the contraction
-                // gsr_blend_md2 documents)
-                const f2 p0 = (f2){q3.z, q3.w} * AA.x;
-                const f2 p1 = pk_mul_b_hi((f2){q4.x, q4.y}, AA);     // col1 * AA.y
-                const f2 pb = (f2){q4.z, q4.w} * AA;
-                crg = pk_fma_b_lo(p0, TT, crg);                      // + (col0 * AA.x) * TT.x
-                crg = pk_fma_b_hi(p1, TT, crg);                      // + (col1 * AA.y) * TT.y
-                cb = __builtin_fmaf(pb.y, TT.y, __builtin_fmaf(pb.x, TT.x, cb));
+                if (FX) {
+                    // the fast blend forms each composite's weight once, both splats in one
+                    // packed product, then rgb += col * (alpha * T) as fused multiply-adds
+                    // in list order: two roundings per term like (col * alpha) * T, in
+                    // another association (colours within the fast blend's 1e-5, not bit
+                    // parity; no decision reads them).  A splat not taken, and the unused
+                    // half-slot of an odd batch (AA.y = 0, zeroed colours), has weight
+                    // 0 * T = 0, and fma(col, 0, acc) = acc for its finite colours
+                    const f2 w = AA * TT;
+                    crg = pk_fma_b_lo((f2){q3.z, q3.w}, w, crg);     // + col0 * (AA.x * TT.x)
+                    crg = pk_fma_b_hi((f2){q4.x, q4.y}, w, crg);     // + col1 * (AA.y * TT.y)
+                    cb = __builtin_fmaf(q4.w, w.y, __builtin_fmaf(q4.z, w.x, cb));
+                } else {
+                    // the three colour products, then rgb += (col * alpha) * T as fused
+                    // multiply-adds in list order (render.cu:337, the contraction
+                    // gsr_blend_md2 documents)
+                    const f2 p0 = (f2){q3.z, q3.w} * AA.x;
+                    const f2 p1 = pk_mul_b_hi((f2){q4.x, q4.y}, AA);     // col1 * AA.y
+                    const f2 pb = (f2){q4.z, q4.w} * AA;
+                    crg = pk_fma_b_lo(p0, TT, crg);                      // + (col0 * AA.x) * TT.x
+                    crg = pk_fma_b_hi(p1, TT, crg);                      // + (col1 * AA.y) * TT.y
+                    cb = __builtin_fmaf(pb.y, TT.y, __builtin_fmaf(pb.x, TT.x, cb));
+                }
                 if (DIAG) {
                     // splat-iterations with no taken lane; pair-iterations in which no live
                     // in-box lane of either splat passes the alpha test's exp argument
