@@ -34,11 +34,13 @@ def cam_for(gsr, W, H, pos=(0, 0, 4), look=(0, 0, 0), fov=50):
     return gsr.make_camera(position=pos, look_at=look, fov_y=fov, aspect=W / H)
 
 
-def render_gpu(gsr, torch, scene, cam, W, H, k=3.0, tiling=None, renderer=None, layout=0, n=None):
+def render_gpu(gsr, torch, scene, cam, W, H, k=3.0, tiling=None, renderer=None, layout=0, n=None, time=None):
+    """One frame (rendered again while gsr_sync reports an overflow); time: of a 4D scene
+    (None: the context's)."""
     r = renderer or gsr.Renderer()
     out = torch.empty(3 * W * H, dtype=torch.float32, device="cuda")
     for _ in range(3):
-        rc = r.render(scene, cam, W, H, out.data_ptr(), k=k, tiling=tiling, layout=layout, n=n)
+        rc = r.render(scene, cam, W, H, out.data_ptr(), k=k, tiling=tiling, layout=layout, n=n, time=time)
         if r.sync() == 0:
             break
     return out.view(3, H, W).cpu().numpy(), r
@@ -133,17 +135,44 @@ CAMS = [dict(pos=(0, 0, 4)), dict(pos=(1.0, 0.5, 3.0), look=(0.2, 0, 0), fov=70)
         dict(pos=(-2.5, -1.0, -3.0))]
 
 
-def check_preprocess_records(gpu, orc, soa, cam, W, H, k=3.0, pairs_of=rect_pairs):
+def temporally_culled(want, got):
+    """The Gaussians of a 4D frame that the oracle's records (of orc.temporal's 3D scene, which
+    has no temporal cull) keep visible and the 4D preprocess left without a tile."""
+    return (want["status"] == 2) & (got["tile_count"] == 0)
+
+
+def same_opacity_bits(got, want, nan_sign_free=False):
+    """Record opacities bit for bit.  nan_sign_free: where both are NaN, the sign bit alone may
+    differ.  A 3D record's opacity is the scene's own bits, but a 4D record's is computed, and
+    the sign of a NaN that an operation makes (0 / 0 from dt = 0 and trbf_scale = 0) is left
+    open by IEEE 754: 0 on gfx950, 1 on the x86-64 hosts of the oracle, flipped once more by
+    the negation in exp(-(u u)).  Nothing reads it: alpha = fminf(NaN, 0.99) either way."""
+    gb, wb = got.view(np.uint32), want.view(np.uint32)
+    if nan_sign_free:
+        both_nan = np.isnan(got) & np.isnan(want)
+        gb, wb = np.where(both_nan, gb & 0x7FFFFFFF, gb), np.where(both_nan, wb & 0x7FFFFFFF, wb)
+    return np.array_equal(gb, wb)
+
+
+def check_preprocess_records(gpu, orc, soa, cam, W, H, k=3.0, pairs_of=rect_pairs, time=None, renderer=None):
     """The records, the depth order, tile_count, the pair list and the tile ranges of one frame
     without tile row spans, bit for bit against the oracle's records.  pairs_of: rect_pairs,
-    or a faster statement of it for scenes of many pairs."""
+    or a faster statement of it for scenes of many pairs.  time: soa is a (49, n) 4D scene,
+    preprocessed at `time` and held against the oracle's records of orc.temporal(soa, time);
+    the Gaussians temporally_culled() names must then have no record, key or pair at all and
+    every other one the oracle's (whether that set is the right one is the caller's to check,
+    on `renderer`'s read_splats).  Returns the oracle's records."""
     scene = gpu.Scene.from_soa(soa)
-    r = gpu.Renderer()
+    r = renderer or gpu.Renderer()
     r.set_tuning(KNOB_TILE_SPANS, 0)   # every tile of every rect (the spans test covers 1)
-    r.preprocess(scene, cam, W, H, k=k)
+    r.preprocess(scene, cam, W, H, k=k, time=time)
     r.sort()
     got = r.read_splats(soa.shape[1])
-    want = orc.preprocess(soa, cam, W, H, k)
+    oracle = orc.preprocess(soa if time is None else orc.temporal(soa, time), cam, W, H, k)
+    want = oracle
+    if time is not None:
+        want = oracle.copy()
+        want["status"][temporally_culled(oracle, got)] = 0
     vis = want["status"] == 2
     assert vis.sum() > 0
     assert np.array_equal(got["tile_count"][~vis], np.zeros((~vis).sum(), np.uint32))
@@ -152,7 +181,7 @@ def check_preprocess_records(gpu, orc, soa, cam, W, H, k=3.0, pairs_of=rect_pair
     w = want[vis]
     assert np.array_equal(g["inv_covar"].view(np.uint32), w["inv_covar"].view(np.uint32))
     assert np.array_equal(g["color"].view(np.uint32), w["color"].view(np.uint32))
-    assert np.array_equal(g["opacity"].view(np.uint32), w["opacity"].view(np.uint32))
+    assert same_opacity_bits(g["opacity"], w["opacity"], nan_sign_free=time is not None)
     assert np.array_equal(g["px_x"], w["px_x"]) and np.array_equal(g["px_y"], w["px_y"])
     assert np.array_equal(g["x_range"] & 0xFFFF, w["aabb"][:, 0]) and np.array_equal(g["x_range"] >> 16, w["aabb"][:, 2])
     assert np.array_equal(g["y_range"] & 0xFFFF, w["aabb"][:, 1]) and np.array_equal(g["y_range"] >> 16, w["aabb"][:, 3])
@@ -176,7 +205,7 @@ def check_preprocess_records(gpu, orc, soa, cam, W, H, k=3.0, pairs_of=rect_pair
     nz = counts > 0
     assert np.array_equal((ranges[nz, 1] - ranges[nz, 0]).astype(np.int64), counts[nz])
     assert (ranges[~nz, 1] == ranges[~nz, 0]).all()
-    return want
+    return oracle
 
 
 @pytest.mark.parametrize("ci", range(len(CAMS)))
@@ -186,11 +215,15 @@ def test_preprocess_records_bit_exact(gpu, orc, torch, c1, ci):
     check_preprocess_records(gpu, orc, soa, cam_for(gpu, W, H, **CAMS[ci]), W, H)
 
 
-def check_tile_spans(gpu, orc, torch, soa, cam, W, H, k=3.0, floor=0.05, pairs_of=rect_pairs):
+def check_tile_spans(gpu, orc, torch, soa, cam, W, H, k=3.0, floor=0.05, pairs_of=rect_pairs, time=None):
     """Tile row spans on against off over one frame (test_tile_spans_drop_only_unreachable_pairs).
     floor: the dropped share of the rect pairs must exceed it, so that spans that do nothing
-    cannot pass.  Returns (rect pairs, dropped pairs, largest alpha of a dropped pair)."""
+    cannot pass.  time: soa is a (49, n) 4D scene rendered at `time`, against the oracle on
+    orc.temporal(soa, time); the full list is then that of the Gaussians the 4D preprocess
+    kept (temporally_culled() of the spans-off frame names the others).
+    Returns (rect pairs, dropped pairs, largest alpha of a dropped pair)."""
     scene = gpu.Scene.from_soa(soa)
+    soa3 = soa if time is None else orc.temporal(soa, time)
     # exact blend: the lists differ, so the fast blend's guard band (which counts list
     # entries) could re-blend different blocks; the exact images must be identical
     r_on, r_off = exact_blend(gpu.Renderer()), exact_blend(gpu.Renderer())
@@ -199,12 +232,16 @@ def check_tile_spans(gpu, orc, torch, soa, cam, W, H, k=3.0, floor=0.05, pairs_o
     r_off.set_tuning(KNOB_TILE_SPANS, 0)
     with pytest.raises(gpu.GsrError):
         r_off.set_tuning(KNOB_TILE_SPANS, 3)
-    got_on, _ = render_gpu(gpu, torch, scene, cam, W, H, k=k, renderer=r_on)
-    got_off, _ = render_gpu(gpu, torch, scene, cam, W, H, k=k, renderer=r_off)
+    got_on, _ = render_gpu(gpu, torch, scene, cam, W, H, k=k, renderer=r_on, time=time)
+    got_off, _ = render_gpu(gpu, torch, scene, cam, W, H, k=k, renderer=r_off, time=time)
     assert np.array_equal(got_on.view(np.uint32), got_off.view(np.uint32))
-    assert_image_parity(got_on, orc.render(soa, cam, W, H, k), exact=True)
-    want = orc.preprocess(soa, cam, W, H, k)
-    full = pairs_of(want, r_on.read_depth_order(soa.shape[1]), W, H)
+    assert_image_parity(got_on, orc.render(soa3, cam, W, H, k), exact=True)
+    want = orc.preprocess(soa3, cam, W, H, k)
+    listed = want
+    if time is not None:
+        listed = want.copy()
+        listed["status"][temporally_culled(want, r_off.read_splats(soa.shape[1]))] = 0
+    full = pairs_of(listed, r_on.read_depth_order(soa.shape[1]), W, H)
     assert np.array_equal(r_off.read_pairs(), full)
     on = r_on.read_pairs()
     assert r_on.pair_count() == full.size          # pair_count: every tile of every rect
