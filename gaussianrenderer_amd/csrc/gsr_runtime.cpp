@@ -64,6 +64,41 @@ extern "C" int gsr_device_available(void) {
     return c > 0 ? 1 : 0;
 }
 
+// ------------------------------------------------------------------ owned device memory
+
+namespace {
+
+// One owned device allocation, freed with its owner.  Converts to T* so launch sites pass it
+// like the raw pointer; move-only, swappable (switch_pre_set swaps the preprocess sets).
+template <typename T>
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        std::swap(p_, o.p_);
+        return *this;
+    }
+    ~DevBuf() {
+        if (p_) (void)hipFree(p_);
+    }
+    operator T*() const { return p_; }
+    T* get() const { return p_; }
+    // Frees what it held, then allocates count elements (0: one); null when hipMalloc fails.
+    int alloc(size_t count) {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+        if (count == 0) count = 1;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p_), sizeof(T) * count));
+        return GSR_OK;
+    }
+
+private:
+    T* p_ = nullptr;
+};
+
+}  // namespace
+
 // ------------------------------------------------------------------ camera (camera.cpp, math.cpp)
 
 namespace {
@@ -275,13 +310,12 @@ extern "C" int gsr_mask_indices(const uint8_t* d_keep, int64_t n, int32_t* d_ind
     if (!d_keep || !d_indices) return set_err(GSR_E_ARG, "gsr_mask_indices: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const uint32_t chunks = gsr::mask_chunks((uint32_t)n);
-    uint32_t* counts = nullptr;   // the chunk counts, then the total
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&counts), sizeof(uint32_t) * ((size_t)chunks + 1)));
+    DevBuf<uint32_t> counts;   // the chunk counts, then the total
+    if (int rc = counts.alloc((size_t)chunks + 1)) return rc;
     uint32_t m = 0;
     hipError_t e = gsr::launch_mask_indices(d_keep, (uint32_t)n, counts, d_indices, s);
     if (e == hipSuccess) e = hipMemcpyAsync(&m, counts + chunks, sizeof m, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(counts);
     if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_mask_indices failed: %s", hipGetErrorString(e));
     *m_out = (int64_t)m;
     return GSR_OK;
@@ -367,21 +401,14 @@ extern "C" void* gsr_scene_select(const void* d_scene, int narrays, int64_t n, c
         return nullptr;
     }
     if (check_scene_block(d_scene, narrays, n, "gsr_scene_select") != GSR_OK) return nullptr;
-    int32_t* idx = d_indices;
-    if (!idx && n > 0) {
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&idx), sizeof(int32_t) * (size_t)n);
-        if (e != hipSuccess) {
-            set_err(GSR_E_HIP, "hipMalloc(%zu) failed: %s", sizeof(int32_t) * (size_t)n, hipGetErrorString(e));
-            return nullptr;
-        }
-    }
+    DevBuf<int32_t> own;   // the index list, when the caller gave none
+    if (!d_indices && n > 0 && own.alloc((size_t)n)) return nullptr;
+    int32_t* idx = d_indices ? d_indices : own.get();
     void* d = nullptr;
     if (gsr_mask_indices(d_keep, n, idx, m_out, stream) == GSR_OK)
         d = scene_gather_checked(d_scene, narrays, n, idx, *m_out, nullptr, stream);
-    if (idx != d_indices) {   // the private index list must outlive the gather that reads it
-        (void)hipStreamSynchronize(static_cast<hipStream_t>(stream));
-        (void)hipFree(idx);
-    }
+    // the private index list must outlive the gather that reads it
+    if (own) (void)hipStreamSynchronize(static_cast<hipStream_t>(stream));
     return d;
 }
 
@@ -517,52 +544,17 @@ gsr_gaussian* loadGaussianCudaFromPly(const std::string& filename, int* out_numG
 
 // ------------------------------------------------------------------ context
 
-struct FrameEvents {
-    int mode;
-    hipEvent_t ev[GSR_NUM_STAGES + 1];
-};
+namespace {
 
-struct gsr_context {
-    std::mutex mu;
-    // capacities (elements)
-    int64_t n_cap = 0, p_cap = 0, t_cap = 0, soa_cap = 0;
-    uint4* rec = nullptr;
-    uint64_t* items[2] = {nullptr, nullptr};
-    // pair buffers: p_cap u64 each, used as {keys: p_cap x 4 B, values: p_cap x 4 B}
-    uint64_t* pairs[2] = {nullptr, nullptr};
-    uint64_t* rect = nullptr;        // per-Gaussian tile rectangle (preprocess output)
-    bool rect_packed = false;        // this frame's rects are packed (binning path, set by gsr_preprocess)
-    uint64_t* srect = nullptr;       // binning path: two u32 rect-payload buffers the depth sort carries
-                                     // (pack_rect), one of them depth-ordered at its end
-    uint16_t* spans = nullptr;       // binning path: per-Gaussian tile row spans (tile_row_spans)
-    bool spans_frame = false;        // this frame's preprocess wrote them (the row pass reads them)
-    uint32_t* hist = nullptr;
-    uint32_t* totals = nullptr;
-    unsigned long long* wg = nullptr;
-    Stats* stats = nullptr;          // device: [0] frame, [1] sticky
-    Stats* hstats = nullptr;         // host-mapped copy of the sticky stats
-    Stats* hstats_dev = nullptr;
-    uint2* ranges = nullptr;
-    float* soa_tmp = nullptr;
-    unsigned long long* consumed = nullptr;   // diagnostics: blend counters (or stamps)
-    int64_t consumed_cap = 0;
-    bool diagnostics = false;
-    int blend_variant = 0;
-    float time = 0.0f;               // frame time for 4D scene blocks
+// Everything that selects kernels or schedules (all settings are bit-identical): what a lane
+// of gsr_render_path inherits from lane 0 (copy_settings).
+struct Settings {
     int tile_items = 16;             // tile sort: items per thread (8 | 16)
     int depth_items = 0;             // depth sort: items per thread (0 = by size | 8 | 16)
     int tile_groups = 1024;          // tile sort: workgroup cap (measured best: 2 tiles of items per group)
     int tile_split_even = 1;         // tile sort: digits split evenly over the passes
     int depth_skip = 1;              // depth sort: skip trailing identity passes (device-side plan)
-    int depth_budget = 4;            // binning path: depth passes launched (adapts to the plan's needs)
-    int depth_budget_streak = 0;     // consecutive checked frames that needed fewer passes than the budget
-    int depth_budget_seen = 0;       // most passes any of those frames needed
-    int passes_launched = 4;         // passes the last depth sort launched
-    uint32_t* dstats = nullptr;      // depth-sort pass plan: 4 final words + 4 per upsweep workgroup
-    uint32_t* nlive = nullptr;       // visible count of the live partition (device word)
     int depth_compact = 2;           // live partition before the depth sort: 0 off, 1 on, 2 4D scenes only
-    bool compact_frame = false;      // this frame's preprocess items went to items[1] for the partition
-    bool last_compact = false;       // the last sorted frame sorted only its visible prefix
     int depth_groups = 0;            // depth sort: workgroup cap (0 = default)
     int tile_binning = 1;            // row + column binning instead of emit + tile sort (grids <= 256 x 256)
     int bin_row_items = 4;           // binning: items per thread of a row-pass tile (4 | 8 | 16)
@@ -572,13 +564,27 @@ struct gsr_context {
                                      // 1 on, 2 on up to kSpansAutoMax Gaussians
     int bin_col_groups = 0;          // binning: column-pass workgroups (chunks are strided over them);
                                      // 0 = by scene size (n / 1024 clamped to 1024..4096)
-    uint64_t* binmeta = nullptr;     // binning: row pair totals (u64 x 256) then row item totals (u32 x 256)
-    uint32_t* cbins = nullptr;       // binning: column counts per chunk (256 x chunks)
-    int64_t cbins_cap = 0;
-    bool last_binned = false;        // the last sorted frame took the binning path
     int blend_exp = 1;               // blend: 1 = fast exp, exact decisions (default); 0 = gsr_blend_expf (bit-exact)
                                      // tests and guarded T tests (re-blends what it cannot vouch for)
     int depth_split = 2;             // GSR_TUNE_DEPTH_SPLIT: 0 off, 1 on, 2 on above kLargeScene Gaussians
+    int blend_band_tiles = 4;        // blend: tiles per spatial band, bands dealt round-robin to the
+                                     // XCDs (0: one contiguous band per XCD)
+    int completion_events = 1;       // 0: no completion event / overflow query (stream capture)
+    int rank_atomic = -1;            // GSR_TUNE_RANK_ATOMIC: 1 = ranks from returning LDS atomics when the
+                                     // device self-check passed, 0 = ballot matching; -1 = not yet set
+                                     // (the environment's GSR_RANK_ATOMIC=0 selects 0, else 1)
+    // bucket depth sort (GSR_TUNE_DEPTH_BUCKETS, gsr_kernels.hip "bucket depth sort")
+    int fuse_rows = 1;               // GSR_TUNE_BUCKET_ROWS: the bucket sort's local kernel counts the row pass
+    int col_chunk = 0;               // GSR_TUNE_COL_CHUNK: 0 = by scene size (col_chunk_for), 1024, 2048
+    int bucket_sort = 1;             // 0 = LSD passes; 1 = bucket sort after the context's first frame
+                                     // (big buckets above 2M, bkt_big); 2 = test hook: as 1 with a local
+                                     // capacity of 64 items (most buckets take the global path); 3 = the
+                                     // small-bucket kind at any size (A/B)
+};
+
+// The depth split's controller: what check_overflow and the preprocess adapt from frame to
+// frame.  An aux frame takes no part in it (aux_frame_locked saves and restores it).
+struct SplitCtl {
     int split_pm = 250;              // split point: phase A bins the nearest split_pm / 1000 of the depth order
     uint32_t split_epoch = 0;        // bumped at every restart of the controller (retry, knob): phase B
                                      // publishes it with the split point, so evidence from before the
@@ -591,26 +597,77 @@ struct gsr_context {
                                      // retry that found no saturating view, back after a clean one)
     float split_off_view[32] = {};   // V and P of the frame the split was turned off on
     float prev_view[32] = {};        // V and P of the previous frame (a still camera: the same twice)
-    bool split_frame = false;        // the sorted frame is split (phase A lists binned by sort_locked)
-    bool split_rebin = false;        // phase B's lists replaced phase A's: a repeated blend bins phase A again
     bool split_seen = false;         // a split frame was blended since the last controller update
     bool split_spec = false;         // speculate: queue no phase B (the split point cannot shrink further
                                      // and 8 checked frames in a row needed none); a frame that then
                                      // leaves a block unsaturated is reported as GSR_E_OVERFLOW
-    bool frame_spec = false;         // the sorted frame is blended without phase B
     float split_view[32] = {};       // V and P of this context's last split frame: a frame speculates
                                      // only with the same camera (its threshold then fits it)
+    bool split_key_ready = false;    // *kcut holds a threshold from an earlier split frame of this context
+};
+
+}  // namespace
+
+struct FrameEvents {
+    int mode;
+    hipEvent_t ev[GSR_NUM_STAGES + 1];
+};
+
+struct gsr_context {
+    std::mutex mu;
+    // capacities (elements)
+    int64_t n_cap = 0, p_cap = 0, t_cap = 0, soa_cap = 0;
+    DevBuf<uint4> rec;
+    DevBuf<uint64_t> items[2];
+    // pair buffers: p_cap u64 each, used as {keys: p_cap x 4 B, values: p_cap x 4 B}
+    DevBuf<uint64_t> pairs[2];
+    DevBuf<uint64_t> rect;           // per-Gaussian tile rectangle (preprocess output)
+    bool rect_packed = false;        // this frame's rects are packed (binning path, set by gsr_preprocess)
+    DevBuf<uint64_t> srect;          // binning path: two u32 rect-payload buffers the depth sort carries
+                                     // (pack_rect), one of them depth-ordered at its end
+    DevBuf<uint16_t> spans;          // binning path: per-Gaussian tile row spans (tile_row_spans)
+    bool spans_frame = false;        // this frame's preprocess wrote them (the row pass reads them)
+    DevBuf<uint32_t> hist;
+    DevBuf<uint32_t> totals;
+    DevBuf<unsigned long long> wg;
+    DevBuf<Stats> stats;             // device: [0] frame, [1] sticky
+    Stats* hstats = nullptr;         // host-mapped copy of the sticky stats
+    Stats* hstats_dev = nullptr;
+    DevBuf<uint2> ranges;
+    DevBuf<float> soa_tmp;
+    DevBuf<unsigned long long> consumed; // diagnostics: blend counters (or stamps)
+    int64_t consumed_cap = 0;
+    bool diagnostics = false;
+    int blend_variant = 0;
+    float time = 0.0f;               // frame time for 4D scene blocks
+    Settings set;                    // the knobs a lane inherits; the knob-backed fields outside it (blend_variant,
+                                     // diagnostics, timing, fail_frame, path_shared_pre, inflight, time) are lane 0's
+    SplitCtl ctl;                    // the depth split's controller (a lane gets split_pm at creation and by its knob)
+    int depth_budget = 4;            // binning path: depth passes launched (adapts to the plan's needs)
+    int depth_budget_streak = 0;     // consecutive checked frames that needed fewer passes than the budget
+    int depth_budget_seen = 0;       // most passes any of those frames needed
+    int passes_launched = 4;         // passes the last depth sort launched
+    DevBuf<uint32_t> dstats;         // depth-sort pass plan: 4 final words + 4 per upsweep workgroup
+    DevBuf<uint32_t> nlive;          // visible count of the live partition (device word)
+    bool compact_frame = false;      // this frame's preprocess items went to items[1] for the partition
+    bool last_compact = false;       // the last sorted frame sorted only its visible prefix
+    DevBuf<uint64_t> binmeta;        // binning: row pair totals (u64 x 256) then row item totals (u32 x 256)
+    DevBuf<uint32_t> cbins;          // binning: column counts per chunk (256 x chunks)
+    int64_t cbins_cap = 0;
+    bool last_binned = false;        // the last sorted frame took the binning path
+    bool split_frame = false;        // the sorted frame is split (phase A lists binned by sort_locked)
+    bool split_rebin = false;        // phase B's lists replaced phase A's: a repeated blend bins phase A again
+    bool frame_spec = false;         // the sorted frame is blended without phase B
     uint32_t split_na = 0;           // phase A's depth-order prefix (count mode) / the split point
     bool split_key = false;          // the preprocess left its items in items[1] for a threshold partition
     bool frame_key = false;          // the sorted frame is split in key mode (near part sorted, far part
                                      // sorted by phase B)
-    bool split_key_ready = false;    // *kcut holds a threshold from an earlier split frame of this context
     bool last_split_key = false;     // the last sorted frame left its far part unsorted (phase B may not run)
-    uint32_t* kcut = nullptr;        // depth split: the next frame's depth threshold (device word)
-    uint32_t* kcut_frame = nullptr;  // depth split: this frame's threshold (the near sort copies it)
-    uint64_t* src_items = nullptr;   // depth split, key mode: the preprocess order (both sorts' pass 0 read it)
-    uint32_t* sat = nullptr;         // depth split, phase B: summed-area table of the unsaturated tiles
-    uint32_t* nfar = nullptr;        // depth split, phase B: far items whose rect touches one (device word)
+    DevBuf<uint32_t> kcut;           // depth split: the next frame's depth threshold (device word)
+    DevBuf<uint32_t> kcut_frame;     // depth split: this frame's threshold (the near sort copies it)
+    DevBuf<uint64_t> src_items;      // depth split, key mode: the preprocess order (both sorts' pass 0 read it)
+    DevBuf<uint32_t> sat;            // depth split, phase B: summed-area table of the unsaturated tiles
+    DevBuf<uint32_t> nfar;           // depth split, phase B: far items whose rect touches one (device word)
     int64_t src_cap = 0;
     uint64_t* pre_out = nullptr;     // where the preprocess wrote its items
     bool records_partial = false;    // the preprocess wrote only the near Gaussians' records
@@ -618,29 +675,17 @@ struct gsr_context {
     const void* pre_scene = nullptr;     // the scene pointer gsr_preprocess was given
     int64_t pre_stride = 0;
     int pre_layout = 0;
-    uint32_t* dstats_far = nullptr;  // depth split: the far sort's pass plan
+    DevBuf<uint32_t> dstats_far;     // depth split: the far sort's pass plan
     int far_launched = 4;            // passes the far sort launched
-    float* tbuf = nullptr;           // depth split: saved transmittance, 64 floats per 8x8 block
-    uint8_t* bflag = nullptr;        // depth split: per block, left unsaturated by phase A
-    uint32_t* gate = nullptr;        // depth split: count of such blocks (device word)
+    DevBuf<float> tbuf;              // depth split: saved transmittance, 64 floats per 8x8 block
+    DevBuf<uint8_t> bflag;           // depth split: per block, left unsaturated by phase A
+    DevBuf<uint32_t> gate;           // depth split: count of such blocks (device word)
     int64_t split_cap = 0;           // blocks tbuf / bflag hold
-    int blend_band_tiles = 4;        // blend: tiles per spatial band, bands dealt round-robin to the
-                                     // XCDs (0: one contiguous band per XCD)
-    int completion_events = 1;       // 0: no completion event / overflow query (stream capture)
-    int rank_atomic = -1;            // GSR_TUNE_RANK_ATOMIC: 1 = ranks from returning LDS atomics when the
-                                     // device self-check passed, 0 = ballot matching; -1 = not yet set
-                                     // (the environment's GSR_RANK_ATOMIC=0 selects 0, else 1)
     bool rank_ok = false;            // the device passed the rank-order self-check (ensure_static)
     bool overflow_seen = false;      // an overflow was reported since the last gsr_sync (which reports it again)
-    // bucket depth sort (GSR_TUNE_DEPTH_BUCKETS, gsr_kernels.hip "bucket depth sort")
-    int fuse_rows = 1;               // GSR_TUNE_BUCKET_ROWS: the bucket sort's local kernel counts the row pass
-    int col_chunk = 0;               // GSR_TUNE_COL_CHUNK: 0 = by scene size (col_chunk_for), 1024, 2048
-    int bucket_sort = 1;             // 0 = LSD passes; 1 = bucket sort after the context's first frame
-                                     // (big buckets above 2M, bkt_big); 2 = test hook: as 1 with a local
-                                     // capacity of 64 items (most buckets take the global path); 3 = the
-                                     // small-bucket kind at any size (A/B)
-    uint32_t* bkt_split = nullptr;   // 2 x kMaxBuckets splitters (double-buffered: read one, write the other)
-    uint4* bkt_rec = nullptr;        // the scatter's 16-B records (n_cap of them, with the items)
+    // bucket depth sort
+    DevBuf<uint32_t> bkt_split;      // 2 x kMaxBuckets splitters (double-buffered: read one, write the other)
+    DevBuf<uint4> bkt_rec;           // the scatter's 16-B records (n_cap of them, with the items)
     int bkt_par = 0;                 // the half the next bucket-sorted frame reads
     int bkt_B = 0;                   // buckets the splitters were made for (0: none yet)
     const void* bkt_scene = nullptr; // the scene they were made from (another scene reseeds them)
@@ -651,11 +696,11 @@ struct gsr_context {
                                      // next binning skips its count kernel (once: the row scan consumes them)
     int split_state_hold = -1;       // >= 0: the sorted frame is an aux frame (gsr_render_aux), and
                                      // GSR_TUNE_DEPTH_SPLIT_STATE reads this, the state of the frame before it
-    float* aux_z = nullptr;          // gsr_render_aux: -Z per Gaussian (the depth channel's values)
+    DevBuf<float> aux_z;             // gsr_render_aux: -Z per Gaussian (the depth channel's values)
     int64_t aux_z_cap = 0;
-    float* rec_grads = nullptr;      // gsr_render_backward_scene without a caller's scratch: ten planes of n floats
+    DevBuf<float> rec_grads;         // gsr_render_backward_scene without a caller's scratch: ten planes of n floats
     int64_t rec_grads_cap = 0;
-    float4* aux_pack = nullptr;      // gsr_render_aux, nfeat > 4: the features interleaved per Gaussian
+    DevBuf<float4> aux_pack;         // gsr_render_aux, nfeat > 4: the features interleaved per Gaussian
     int64_t aux_pack_cap = 0;
     int fail_frame = 0;              // GSR_TUNE_FAIL_FRAME: gsr_render_path fails this frame (> 0) once
     uint32_t* fstatus = nullptr;     // the current frame's validity word (gsr_render_path_status; device,
@@ -678,7 +723,7 @@ struct gsr_context {
     std::vector<FrameEvents> ev_frames;
     FrameEvents cur{};
     // drop-in helpers
-    float* out_tmp = nullptr;
+    DevBuf<float> out_tmp;
     int64_t out_cap = 0;
     // frames in flight (gsr_render_path): lane 0 is this context on the caller's
     // stream; lane l >= 1 is a private child context (own workspace) on its own
@@ -694,10 +739,10 @@ struct gsr_context {
     // used the other one.
     int path_shared_pre = 1;
     int64_t shared_launches = 0;     // GSR_TUNE_PATH_SHARED_LAUNCHES (lane 0 counts)
-    uint4* alt_rec = nullptr;
-    uint64_t* alt_items = nullptr;
-    uint64_t* alt_rect = nullptr;
-    uint16_t* alt_spans = nullptr;
+    DevBuf<uint4> alt_rec;
+    DevBuf<uint64_t> alt_items;
+    DevBuf<uint64_t> alt_rect;
+    DevBuf<uint16_t> alt_spans;
     int64_t alt_cap = 0;
     hipEvent_t alt_ev = nullptr;
     hipEvent_t pre_ev = nullptr;     // lane 0: after a group's shared launches
@@ -719,8 +764,8 @@ constexpr int kSplitRetryMax = 1 << 14;
 // gsr_render / gsr_render_path decide it per frame, the stage API never).  Its two blend
 // phases always run the exact blend, whatever GSR_TUNE_BLEND_EXP says for other frames.
 bool split_enabled(const gsr_context* c, int64_t n) {
-    return n > 0 && c->blend_variant != 3 && c->split_pm < 1000 &&
-           (c->depth_split == 1 || (c->depth_split == 2 && n > kLargeScene));
+    return n > 0 && c->blend_variant != 3 && c->ctl.split_pm < 1000 &&
+           (c->set.depth_split == 1 || (c->set.depth_split == 2 && n > kLargeScene));
 }
 
 // Buckets of the bucket depth sort for n items: about 1,024 items per bucket (local sorts
@@ -740,29 +785,20 @@ int bkt_count(int64_t n) {
 // (profiles/r06k_big_buckets_c3_orbit.txt).  Knob 28: 1 (default) both kinds by size; 2 the
 // test hook (64-item capacity, either kind); 3 the small-bucket kind at any size (A/B).
 constexpr int64_t kBucketSortMaxN = (int64_t)2048 * 1024;
-bool bkt_applies(const gsr_context* c, int64_t n) { return n > 0 && c->bucket_sort != 0; }
-bool bkt_big(const gsr_context* c, int64_t n) { return c->bucket_sort != 3 && n > kBucketSortMaxN; }
+bool bkt_applies(const gsr_context* c, int64_t n) { return n > 0 && c->set.bucket_sort != 0; }
+bool bkt_big(const gsr_context* c, int64_t n) { return c->set.bucket_sort != 3 && n > kBucketSortMaxN; }
 int bkt_count(const gsr_context* c, int64_t n) { return bkt_big(c, n) ? gsr::kBigBuckets : bkt_count(n); }
 
 // Row items per column-pass chunk (GSR_TUNE_COL_CHUNK 0): 1,024 up to the same 2M
 // Gaussians (config 2: column scatter 26.0 -> 21.6 us, chain -2 us), 2,048 above (config 3:
 // the doubled chunk count costs the count and scan +10 us), profiles/r05_ab_col_chunk.txt.
 int col_chunk_for(const gsr_context* c) {
-    return c->col_chunk ? c->col_chunk : (c->n <= kBucketSortMaxN ? 1024 : 2048);
+    return c->set.col_chunk ? c->set.col_chunk : (c->n <= kBucketSortMaxN ? 1024 : 2048);
 }
 
 int groups_for(int64_t n, int64_t per) {
     int64_t g = (n + per - 1) / per;
     return (int)std::max<int64_t>(1, std::min<int64_t>(g, gsr::kMaxSortGroups));
-}
-
-template <typename T>
-int realloc_dev(T** p, size_t count) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    if (count == 0) count = 1;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), sizeof(T) * count));
-    return GSR_OK;
 }
 
 // ---- rank-order self-check, once per process and device (gsr_probes.hip
@@ -800,28 +836,28 @@ int default_rank_atomic() {
 }
 
 int ensure_static(gsr_context* c) {
-    if (c->rank_atomic < 0) c->rank_atomic = default_rank_atomic();
+    if (c->set.rank_atomic < 0) c->set.rank_atomic = default_rank_atomic();
     if (c->hist) return GSR_OK;
     {
         RankCheck rk;
         if (int rc = rank_check_device(&rk)) return rc;
         c->rank_ok = rk.state == 1;
     }
-    if (int rc = realloc_dev(&c->hist, 256 * (size_t)gsr::kMaxSortGroups)) return rc;
+    if (int rc = c->hist.alloc(256 * (size_t)gsr::kMaxSortGroups)) return rc;
     // LSD digit totals / bucket totals + bucket starts
-    if (int rc = realloc_dev(&c->totals, 2 * (size_t)gsr::kMaxBuckets + 2)) return rc;
-    if (int rc = realloc_dev(&c->bkt_split, 2 * (size_t)gsr::kMaxBuckets)) return rc;
-    if (int rc = realloc_dev(&c->wg, (size_t)gsr::kMaxSortGroups)) return rc;
-    if (int rc = realloc_dev(&c->stats, 2)) return rc;
-    if (int rc = realloc_dev(&c->dstats, 4 + 4 * (size_t)gsr::kMaxSortGroups)) return rc;
-    if (int rc = realloc_dev(&c->nlive, 1)) return rc;
-    if (int rc = realloc_dev(&c->binmeta, 256 + 128)) return rc;
-    if (int rc = realloc_dev(&c->gate, 1)) return rc;
-    if (int rc = realloc_dev(&c->kcut, 1)) return rc;
-    if (int rc = realloc_dev(&c->kcut_frame, 1)) return rc;
-    if (int rc = realloc_dev(&c->nfar, 1)) return rc;
-    if (int rc = realloc_dev(&c->sat, 257 * 257)) return rc;   // grids <= 256 x 256 tiles
-    if (int rc = realloc_dev(&c->dstats_far, 4 + 4 * (size_t)gsr::kMaxSortGroups)) return rc;
+    if (int rc = c->totals.alloc(2 * (size_t)gsr::kMaxBuckets + 2)) return rc;
+    if (int rc = c->bkt_split.alloc(2 * (size_t)gsr::kMaxBuckets)) return rc;
+    if (int rc = c->wg.alloc((size_t)gsr::kMaxSortGroups)) return rc;
+    if (int rc = c->stats.alloc(2)) return rc;
+    if (int rc = c->dstats.alloc(4 + 4 * (size_t)gsr::kMaxSortGroups)) return rc;
+    if (int rc = c->nlive.alloc(1)) return rc;
+    if (int rc = c->binmeta.alloc(256 + 128)) return rc;
+    if (int rc = c->gate.alloc(1)) return rc;
+    if (int rc = c->kcut.alloc(1)) return rc;
+    if (int rc = c->kcut_frame.alloc(1)) return rc;
+    if (int rc = c->nfar.alloc(1)) return rc;
+    if (int rc = c->sat.alloc(257 * 257)) return rc;   // grids <= 256 x 256 tiles
+    if (int rc = c->dstats_far.alloc(4 + 4 * (size_t)gsr::kMaxSortGroups)) return rc;
     HIP_TRY(hipMemset(c->kcut, 0xff, sizeof(uint32_t)));
     HIP_TRY(hipMemset(c->stats, 0, 2 * sizeof(Stats)));
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->hstats), sizeof(Stats), hipHostMallocMapped));
@@ -835,20 +871,20 @@ int ensure_n(gsr_context* c, int64_t n) {
     if (n <= c->n_cap) return GSR_OK;
     const int64_t cap = std::max<int64_t>(n, 1024);
     HIP_TRY(hipDeviceSynchronize());
-    if (int rc = realloc_dev(&c->rec, 4 * (size_t)cap)) return rc;
-    if (int rc = realloc_dev(&c->items[0], (size_t)cap)) return rc;
-    if (int rc = realloc_dev(&c->items[1], (size_t)cap)) return rc;
-    if (int rc = realloc_dev(&c->rect, (size_t)cap)) return rc;
-    if (int rc = realloc_dev(&c->srect, (size_t)cap)) return rc;
-    if (int rc = realloc_dev(&c->spans, (size_t)cap)) return rc;
+    if (int rc = c->rec.alloc(4 * (size_t)cap)) return rc;
+    if (int rc = c->items[0].alloc((size_t)cap)) return rc;
+    if (int rc = c->items[1].alloc((size_t)cap)) return rc;
+    if (int rc = c->rect.alloc((size_t)cap)) return rc;
+    if (int rc = c->srect.alloc((size_t)cap)) return rc;
+    if (int rc = c->spans.alloc((size_t)cap)) return rc;
     // the bucket sort's 16-B records (allocated with the items, so gsr_reserve covers them
     // and a captured frame never allocates)
-    if (int rc = realloc_dev(&c->bkt_rec, (size_t)cap)) return rc;
+    if (int rc = c->bkt_rec.alloc((size_t)cap)) return rc;
     c->n_cap = cap;
     if (c->p_cap < 4 * cap) {
         const int64_t pc = std::min<int64_t>(std::max<int64_t>(4 * cap, 1 << 20), 0xffffffffLL);
-        if (int rc = realloc_dev(&c->pairs[0], (size_t)pc)) return rc;
-        if (int rc = realloc_dev(&c->pairs[1], (size_t)pc)) return rc;
+        if (int rc = c->pairs[0].alloc((size_t)pc)) return rc;
+        if (int rc = c->pairs[1].alloc((size_t)pc)) return rc;
         c->p_cap = pc;
     }
     return GSR_OK;
@@ -858,8 +894,8 @@ int ensure_pairs(gsr_context* c, int64_t p) {
     if (p <= c->p_cap) return GSR_OK;
     const int64_t pc = std::min<int64_t>(p, 0xffffffffLL);
     HIP_TRY(hipDeviceSynchronize());
-    if (int rc = realloc_dev(&c->pairs[0], (size_t)pc)) return rc;
-    if (int rc = realloc_dev(&c->pairs[1], (size_t)pc)) return rc;
+    if (int rc = c->pairs[0].alloc((size_t)pc)) return rc;
+    if (int rc = c->pairs[1].alloc((size_t)pc)) return rc;
     c->p_cap = pc;
     return GSR_OK;
 }
@@ -867,7 +903,7 @@ int ensure_pairs(gsr_context* c, int64_t p) {
 int ensure_tiles(gsr_context* c, int64_t t) {
     if (t <= c->t_cap) return GSR_OK;
     HIP_TRY(hipDeviceSynchronize());
-    if (int rc = realloc_dev(&c->ranges, (size_t)t)) return rc;
+    if (int rc = c->ranges.alloc((size_t)t)) return rc;
     c->t_cap = t;
     return GSR_OK;
 }
@@ -876,7 +912,7 @@ int ensure_tiles(gsr_context* c, int64_t t) {
 int ensure_src(gsr_context* c, int64_t n) {
     if (n <= c->src_cap) return GSR_OK;
     HIP_TRY(hipDeviceSynchronize());
-    if (int rc = realloc_dev(&c->src_items, (size_t)std::max<int64_t>(n, 1024))) return rc;
+    if (int rc = c->src_items.alloc((size_t)std::max<int64_t>(n, 1024))) return rc;
     c->src_cap = std::max<int64_t>(n, 1024);
     return GSR_OK;
 }
@@ -886,8 +922,8 @@ int ensure_split(gsr_context* c) {
     const int64_t blocks = 4 * (int64_t)c->ntiles;
     if (blocks <= c->split_cap) return GSR_OK;
     HIP_TRY(hipDeviceSynchronize());
-    if (int rc = realloc_dev(&c->tbuf, 64 * (size_t)blocks)) return rc;
-    if (int rc = realloc_dev(&c->bflag, (size_t)blocks)) return rc;
+    if (int rc = c->tbuf.alloc(64 * (size_t)blocks)) return rc;
+    if (int rc = c->bflag.alloc((size_t)blocks)) return rc;
     c->split_cap = blocks;
     return GSR_OK;
 }
@@ -896,7 +932,7 @@ int ensure_soa(gsr_context* c, int64_t n) {
     const int64_t need = (int64_t)GSR_SCENE_NARRAYS * scene_stride(n);
     if (need <= c->soa_cap) return GSR_OK;
     HIP_TRY(hipDeviceSynchronize());
-    if (int rc = realloc_dev(&c->soa_tmp, (size_t)need)) return rc;
+    if (int rc = c->soa_tmp.alloc((size_t)need)) return rc;
     c->soa_cap = need;
     return GSR_OK;
 }
@@ -931,15 +967,15 @@ int split_state(const gsr_context* c) {
 }
 
 // The split point and the controller's epoch as phase B publishes them (Stats::split_pm).
-uint32_t split_tag(const gsr_context* c) { return (uint32_t)c->split_pm | ((c->split_epoch & 0xffffu) << 16); }
+uint32_t split_tag(const gsr_context* c) { return (uint32_t)c->ctl.split_pm | ((c->ctl.split_epoch & 0xffffu) << 16); }
 
 // Depth split point after a frame that needed phase B: up by half, floor at 5/4 of the
 // old point, no speculation.
 void split_grow(gsr_context* c) {
-    c->split_floor = std::min(1000, c->split_pm * 5 / 4 + 1);
-    c->split_pm = std::min(1000, c->split_pm * 3 / 2 + 1);
-    c->split_clean = 0;
-    c->split_spec = false;
+    c->ctl.split_floor = std::min(1000, c->ctl.split_pm * 5 / 4 + 1);
+    c->ctl.split_pm = std::min(1000, c->ctl.split_pm * 3 / 2 + 1);
+    c->ctl.split_clean = 0;
+    c->ctl.split_spec = false;
 }
 
 void hv_clear_spec(gsr_context* c) {
@@ -957,7 +993,7 @@ int check_overflow(gsr_context* c, bool blocking) {
         // with completion events off (stream capture) no event marks finished work: a
         // blocking check (gsr_sync) drains the device and reads the sticky words anyway,
         // so an overflow or a speculative miss is still reported there
-        if (!blocking || c->completion_events || !c->hstats) return GSR_OK;
+        if (!blocking || c->set.completion_events || !c->hstats) return GSR_OK;
         HIP_TRY(hipDeviceSynchronize());
     } else if (blocking) {
         HIP_TRY(hipEventSynchronize(c->done_ev));
@@ -981,33 +1017,33 @@ int check_overflow(gsr_context* c, bool blocking) {
         return set_err(GSR_E_OVERFLOW, "depth split: a frame rendered without phase B left blocks unsaturated; "
                                        "re-render");
     }
-    if (!s.overflow && c->split_seen) {
+    if (!s.overflow && c->ctl.split_seen) {
         // depth split point: up by half when phase A left blocks unsaturated (phase B
         // ran), down by an eighth after 8 checked frames in a row that needed no phase B,
         // never below 5/4 of the last point that needed it; when it cannot shrink any
         // further, the next frames speculate (no phase B queued)
-        c->split_seen = false;
+        c->ctl.split_seen = false;
         const int64_t u = hv->split_unsat;
         if (hv->split_pm != split_tag(c)) {
             // the newest phase B ran at an earlier split point (frames in flight): no
             // evidence about the current one yet
         } else if (u == 0) {
-            c->split_retry = kSplitRetry;   // a saturating view: the next turn-off retries soon
-            if (++c->split_clean >= 8) {
-                c->split_clean = 0;
-                const int next = std::max(std::max(kSplitMinPm, c->split_floor), c->split_pm * 7 / 8);
-                if (next >= c->split_pm) c->split_spec = true;
-                c->split_pm = next;
+            c->ctl.split_retry = kSplitRetry;   // a saturating view: the next turn-off retries soon
+            if (++c->ctl.split_clean >= 8) {
+                c->ctl.split_clean = 0;
+                const int next = std::max(std::max(kSplitMinPm, c->ctl.split_floor), c->ctl.split_pm * 7 / 8);
+                if (next >= c->ctl.split_pm) c->ctl.split_spec = true;
+                c->ctl.split_pm = next;
             }
         } else {
-            const int pm_old = c->split_pm;
+            const int pm_old = c->ctl.split_pm;
             split_grow(c);   // phase A left blocks unsaturated
             // at or above the starting point, 2 % of the blocks or more left unsaturated
             // means tiles that see past the scene, which no split point saturates (phase B
             // would run on every frame, at a cost above the unsplit frame's): off at once
             // rather than in four growth steps (automatic mode; a forced split keeps growing)
-            if (c->depth_split == 2 && pm_old >= 250 && u * 50 >= 4 * (int64_t)c->ntiles) c->split_pm = 1000;
-            if (c->split_pm >= 1000) {
+            if (c->set.depth_split == 2 && pm_old >= 250 && u * 50 >= 4 * (int64_t)c->ntiles) c->ctl.split_pm = 1000;
+            if (c->ctl.split_pm >= 1000) {
                 // the split turned itself off: the next frames list the whole order's pairs.
                 // Size the pair buffer for them now (the split frames' pairs scaled to the
                 // whole order) rather than overflow and re-render a chunk
@@ -1103,8 +1139,8 @@ int ceil_log2(int64_t v) {
 extern "C" gsr_context* gsr_create(void) {
     gsr_context* c = new gsr_context();
     const char* e = std::getenv("GSR_BLEND_EXP");
-    if (e && e[0] == '0') c->blend_exp = 0;   // the exact blend (bit-identical to the oracle)
-    if (e && e[0] == '1') c->blend_exp = 1;
+    if (e && e[0] == '0') c->set.blend_exp = 0;   // the exact blend (bit-identical to the oracle)
+    if (e && e[0] == '1') c->set.blend_exp = 1;
     return c;
 }
 
@@ -1118,23 +1154,13 @@ extern "C" void gsr_destroy(gsr_context* c) {
     if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
     if (c->alt_ev) (void)hipEventDestroy(c->alt_ev);
     if (c->pre_ev) (void)hipEventDestroy(c->pre_ev);
-    for (auto* p : {(void*)c->alt_rec, (void*)c->alt_items, (void*)c->alt_rect, (void*)c->alt_spans})
-        if (p) (void)hipFree(p);
-    for (auto* p : {(void*)c->rec, (void*)c->items[0], (void*)c->items[1], (void*)c->rect, (void*)c->pairs[0],
-                    (void*)c->pairs[1], (void*)c->hist, (void*)c->totals, (void*)c->wg, (void*)c->stats, (void*)c->dstats,
-                    (void*)c->ranges, (void*)c->soa_tmp, (void*)c->out_tmp, (void*)c->consumed, (void*)c->binmeta,
-                    (void*)c->cbins, (void*)c->srect, (void*)c->spans, (void*)c->nlive, (void*)c->tbuf,
-                    (void*)c->bflag, (void*)c->gate, (void*)c->kcut, (void*)c->dstats_far, (void*)c->kcut_frame,
-                    (void*)c->src_items, (void*)c->sat, (void*)c->nfar, (void*)c->bkt_rec, (void*)c->aux_z, (void*)c->aux_pack,
-                    (void*)c->rec_grads})
-        if (p) (void)hipFree(p);
     if (c->hstats) (void)hipHostFree(c->hstats);
     if (c->done_ev) (void)hipEventDestroy(c->done_ev);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     for (auto& f : c->ev_frames)
         for (auto e : f.ev)
             if (e) (void)hipEventDestroy(e);
-    delete c;
+    delete c;   // the device buffers (DevBuf members) go here
 }
 
 extern "C" int gsr_reserve(gsr_context* c, int64_t n, int64_t pairs) {
@@ -1184,34 +1210,34 @@ static int preprocess_plan(gsr_context* c, const void* scene, int layout, int64_
     // from another view, and the controller's evidence lags the frames queued ahead of
     // it), it is tried again from the starting point; each retry doubles the next wait,
     // up to kSplitRetryMax, until a retry finds a view whose tiles all saturate
-    const bool still = std::memcmp(c->prev_view, c->fr.V, sizeof c->fr.V) == 0 &&
-                       std::memcmp(c->prev_view + 16, c->fr.P, sizeof c->fr.P) == 0;
-    std::memcpy(c->prev_view, c->fr.V, sizeof c->fr.V);
-    std::memcpy(c->prev_view + 16, c->fr.P, sizeof c->fr.P);
-    if (c->split_pm >= 1000 && (c->depth_split == 1 || (c->depth_split == 2 && n > kLargeScene))) {
-        if (c->split_off_frames == 0) {
-            std::memcpy(c->split_off_view, c->fr.V, sizeof c->fr.V);
-            std::memcpy(c->split_off_view + 16, c->fr.P, sizeof c->fr.P);
+    const bool still = std::memcmp(c->ctl.prev_view, c->fr.V, sizeof c->fr.V) == 0 &&
+                       std::memcmp(c->ctl.prev_view + 16, c->fr.P, sizeof c->fr.P) == 0;
+    std::memcpy(c->ctl.prev_view, c->fr.V, sizeof c->fr.V);
+    std::memcpy(c->ctl.prev_view + 16, c->fr.P, sizeof c->fr.P);
+    if (c->ctl.split_pm >= 1000 && (c->set.depth_split == 1 || (c->set.depth_split == 2 && n > kLargeScene))) {
+        if (c->ctl.split_off_frames == 0) {
+            std::memcpy(c->ctl.split_off_view, c->fr.V, sizeof c->fr.V);
+            std::memcpy(c->ctl.split_off_view + 16, c->fr.P, sizeof c->fr.P);
         }
-        if (c->split_retry == 0) c->split_retry = kSplitRetry;
-        c->split_off_frames = std::min(c->split_off_frames + 1, 1 << 30);
-        const bool moved = std::memcmp(c->split_off_view, c->fr.V, sizeof c->fr.V) != 0 ||
-                           std::memcmp(c->split_off_view + 16, c->fr.P, sizeof c->fr.P) != 0;
-        if (c->split_off_frames >= c->split_retry && moved && still) {
-            c->split_retry = std::min(2 * c->split_retry, kSplitRetryMax);
-            c->split_off_frames = 0;
-            c->split_pm = 250;
-            c->split_epoch++;
-            c->split_floor = 0;
-            c->split_clean = 0;
-            c->split_key_ready = false;
+        if (c->ctl.split_retry == 0) c->ctl.split_retry = kSplitRetry;
+        c->ctl.split_off_frames = std::min(c->ctl.split_off_frames + 1, 1 << 30);
+        const bool moved = std::memcmp(c->ctl.split_off_view, c->fr.V, sizeof c->fr.V) != 0 ||
+                           std::memcmp(c->ctl.split_off_view + 16, c->fr.P, sizeof c->fr.P) != 0;
+        if (c->ctl.split_off_frames >= c->ctl.split_retry && moved && still) {
+            c->ctl.split_retry = std::min(2 * c->ctl.split_retry, kSplitRetryMax);
+            c->ctl.split_off_frames = 0;
+            c->ctl.split_pm = 250;
+            c->ctl.split_epoch++;
+            c->ctl.split_floor = 0;
+            c->ctl.split_clean = 0;
+            c->ctl.split_key_ready = false;
         }
     } else {
-        c->split_off_frames = 0;
+        c->ctl.split_off_frames = 0;
     }
     // depth split with a depth threshold (a threshold exists from an earlier split
     // frame): the items go to src_items, which both sorts' pass 0 read
-    c->split_key = split_enabled(c, n) && c->split_key_ready && c->tile_binning && c->fr.tiles_x <= 256 &&
+    c->split_key = split_enabled(c, n) && c->ctl.split_key_ready && c->set.tile_binning && c->fr.tiles_x <= 256 &&
                    c->fr.tiles_y <= 256;
     // live partition (global depth sort on the binning path): the items go to
     // items[1] and the partition writes the visible-first order into items[0]
@@ -1227,27 +1253,27 @@ static int preprocess_plan(gsr_context* c, const void* scene, int layout, int64_
     // host-mapped and lags by the frames in flight; the test hook 2 (capacity 64) keeps them.
     {
         const unsigned int work = c->hstats ? ((const volatile Stats*)c->hstats)->bkt_over_work : 0u;
-        const bool spike = c->bucket_sort != 2 && (int64_t)(work - c->bkt_work_seen) > n / 8;
+        const bool spike = c->set.bucket_sort != 2 && (int64_t)(work - c->bkt_work_seen) > n / 8;
         c->bkt_work_seen = work;
         if (c->bkt_B && (spike || c->bkt_scene != scene)) c->bkt_B = 0;
     }
-    c->bds_frame = bkt_applies(c, n) && !c->split_key && c->bucket_sort && c->bkt_B == bkt_count(c, n) && c->tile_binning &&
-                   c->fr.tiles_x <= 256 && c->fr.tiles_y <= 256;
+    c->bds_frame = bkt_applies(c, n) && !c->split_key && c->set.bucket_sort && c->bkt_B == bkt_count(c, n) &&
+                   c->set.tile_binning && c->fr.tiles_x <= 256 && c->fr.tiles_y <= 256;
     c->compact_frame = n > 0 && !c->split_key && !c->bds_frame &&
-                       (c->depth_compact == 1 || (c->depth_compact == 2 && layout == GSR_LAYOUT_SCENE_BLOCK_4D)) &&
-                       c->tile_binning && c->fr.tiles_x <= 256 && c->fr.tiles_y <= 256;
+                       (c->set.depth_compact == 1 || (c->set.depth_compact == 2 && layout == GSR_LAYOUT_SCENE_BLOCK_4D)) &&
+                       c->set.tile_binning && c->fr.tiles_x <= 256 && c->fr.tiles_y <= 256;
     // the binning path takes the tile rects packed to 4 B (pack_rect), the pair path 8 B;
     // the sort follows the path chosen here (rect_packed)
-    c->rect_packed = c->tile_binning && c->fr.tiles_x <= 256 && c->fr.tiles_y <= 256;
+    c->rect_packed = c->set.tile_binning && c->fr.tiles_x <= 256 && c->fr.tiles_y <= 256;
     // tile row spans: the row pass gathers each source's 2-B code by index; up to 1.5M
     // Gaussians the codes (<= 3 MB) stay in an XCD's 4-MB L2 and the gather is cheap:
     // config 2 (1M) +0.8 % one frame at a time, +1.2 % in flight; config 5 (2M) -1 % in
     // flight, config 3 (5M) -3 / -6 % (profiles/r02_ab_tile_spans.txt)
-    c->spans_frame = c->rect_packed && (c->tile_spans == 1 || (c->tile_spans == 2 && n <= kLargeScene));
+    c->spans_frame = c->rect_packed && (c->set.tile_spans == 1 || (c->set.tile_spans == 2 && n <= kLargeScene));
     // key mode: records only for the Gaussians nearer than the threshold (the far ones
     // are written by a second pass if phase B or a one-phase sort needs them)
     // (speculative frames only: a frame that queues phase B needs every record there)
-    c->records_partial = c->split_key && c->split_spec && !c->spans_frame;
+    c->records_partial = c->split_key && c->ctl.split_spec && !c->spans_frame;
     c->pre_arrays = arrays;
     c->pre_scene = scene;
     c->pre_stride = stride;
@@ -1286,7 +1312,7 @@ static int preprocess_locked(gsr_context* c, const void* scene, int layout, int6
 
 static void* pair_keys(gsr_context* c, int b) { return c->pairs[b]; }
 static uint32_t* pair_vals(gsr_context* c, int b) {
-    return reinterpret_cast<uint32_t*>(c->pairs[b]) + c->p_cap;
+    return reinterpret_cast<uint32_t*>(c->pairs[b].get()) + c->p_cap;
 }
 
 // Column-pass chunk counts for the current capacity and grid.
@@ -1294,18 +1320,18 @@ static int ensure_cbins(gsr_context* c) {
     const int64_t need = 256 * (int64_t)gsr::bin_col_chunks_max((uint32_t)c->p_cap, c->fr.tiles_y);
     if (need > c->cbins_cap) {
         HIP_TRY(hipDeviceSynchronize());
-        if (int rc = realloc_dev(&c->cbins, (size_t)need)) return rc;
+        if (int rc = c->cbins.alloc((size_t)need)) return rc;
         c->cbins_cap = need;
     }
     return GSR_OK;
 }
 
 // Ranks from returning LDS atomics: asked for (GSR_TUNE_RANK_ATOMIC) and verified on the device.
-static bool rank_atomic_on(const gsr_context* c) { return c->rank_atomic > 0 && c->rank_ok; }
+static bool rank_atomic_on(const gsr_context* c) { return c->set.rank_atomic > 0 && c->rank_ok; }
 
 // Rect payload buffer b (0 or 1) of the binning's depth sort: the two u32 halves of srect.
 static uint32_t* pay_buf(gsr_context* c, int b) {
-    return reinterpret_cast<uint32_t*>(c->srect) + (b ? c->n_cap : 0);
+    return reinterpret_cast<uint32_t*>(c->srect.get()) + (b ? c->n_cap : 0);
 }
 
 // Global stable depth sort of the preprocess items (key << 32 | index), 4 x 8-bit
@@ -1325,8 +1351,8 @@ static int depth_sort_locked(gsr_context* c, bool with_rects, bool plain = false
             uint32_t* s_in = c->bkt_split + (size_t)c->bkt_par * gsr::kMaxBuckets;
             uint32_t* s_out = c->bkt_split + (size_t)(c->bkt_par ^ 1) * gsr::kMaxBuckets;
             HIP_TRY(gsr::launch_bucket_sort_big(c->pre_out, c->items[0], c->items[1], n, B, G, s_in, s_out, c->hist,
-                                                c->totals, reinterpret_cast<const uint32_t*>(c->rect), pay_buf(c, 0),
-                                                pay_buf(c, 1), rank_atomic_on(c), c->bucket_sort == 2 ? 64u : 16384u,
+                                                c->totals, reinterpret_cast<const uint32_t*>(c->rect.get()), pay_buf(c, 0),
+                                                pay_buf(c, 1), rank_atomic_on(c), c->set.bucket_sort == 2 ? 64u : 16384u,
                                                 c->hstats_dev ? &c->hstats_dev->bkt_over : nullptr, c->stream,
                                                 c->bkt_rec));
             c->bkt_rows_fused = false;
@@ -1342,12 +1368,12 @@ static int depth_sort_locked(gsr_context* c, bool with_rects, bool plain = false
         const int G = std::min(groups_for(c->n, gsr::kMaxBucketCap), gsr::kMaxBucketGroups);
         // a plain frame (one binning over the whole order): the local sorts also count the
         // row pass's items and pairs per bucket, which becomes the row pass's chunk
-        const bool fuse = plain && c->fuse_rows && (int64_t)512 * B <= 256 * (int64_t)gsr::kMaxSortGroups;
+        const bool fuse = plain && c->set.fuse_rows && (int64_t)512 * B <= 256 * (int64_t)gsr::kMaxSortGroups;
         uint32_t* s_in = c->bkt_split + (size_t)c->bkt_par * gsr::kMaxBuckets;
         uint32_t* s_out = c->bkt_split + (size_t)(c->bkt_par ^ 1) * gsr::kMaxBuckets;
         HIP_TRY(gsr::launch_bucket_sort(c->pre_out, c->items[0], c->items[1], n, B, G, s_in, s_out, c->hist,
-                                        c->totals, reinterpret_cast<const uint32_t*>(c->rect), pay_buf(c, 0),
-                                        pay_buf(c, 1), rank_atomic_on(c), c->bucket_sort == 2 ? 64u : gsr::kMaxBucketCap,
+                                        c->totals, reinterpret_cast<const uint32_t*>(c->rect.get()), pay_buf(c, 0),
+                                        pay_buf(c, 1), rank_atomic_on(c), c->set.bucket_sort == 2 ? 64u : gsr::kMaxBucketCap,
                                         c->hstats_dev ? &c->hstats_dev->bkt_over : nullptr, c->stream,
                                         fuse ? c->fr.tiles_y : 0, c->bkt_rec));
         c->bkt_rows_fused = fuse;
@@ -1369,19 +1395,19 @@ static int depth_sort_locked(gsr_context* c, bool with_rects, bool plain = false
     // nlive; about 2 x the split point's items), the far part is sorted inside phase B
     const bool key = with_rects && c->split_key;
     const int64_t n_sorted =
-        key ? std::min<int64_t>(c->n, std::max<int64_t>(2 * ((int64_t)c->n * c->split_pm / 1000), 65536)) : c->n;
-    const int di = c->depth_items ? c->depth_items : (n_sorted < (int64_t(4) << 20) ? 8 : 16);
+        key ? std::min<int64_t>(c->n, std::max<int64_t>(2 * ((int64_t)c->n * c->ctl.split_pm / 1000), 65536)) : c->n;
+    const int di = c->set.depth_items ? c->set.depth_items : (n_sorted < (int64_t(4) << 20) ? 8 : 16);
     int gd = groups_for(key ? c->n : n_sorted, 256 * di);   // pass 0 reads all n
     int gd_near = groups_for(n_sorted, 256 * di);
-    if (c->depth_groups) {
-        gd = std::min(gd, c->depth_groups);
-        gd_near = std::min(gd_near, c->depth_groups);
+    if (c->set.depth_groups) {
+        gd = std::min(gd, c->set.depth_groups);
+        gd_near = std::min(gd_near, c->set.depth_groups);
     }
     const bool part = with_rects && c->compact_frame;
     // visible items first (index order) into items[0]; the passes sort only those
     if (part)
         HIP_TRY(gsr::launch_partition(c->pre_out, n, std::min(groups_for(c->n, 4096), gsr::kMaxSortGroups), c->hist,
-                                      c->nlive, c->items[0], reinterpret_cast<const uint32_t*>(c->rect),
+                                      c->nlive, c->items[0], reinterpret_cast<const uint32_t*>(c->rect.get()),
                                       pay_buf(c, 0), pay_buf(c, 1), c->stream));
     // a repeated sort of a key-mode frame starts again from the preprocess order
     const bool resort_src = !key && !part && c->have_sort && c->last_split_key;
@@ -1401,7 +1427,7 @@ static int depth_sort_locked(gsr_context* c, bool with_rects, bool plain = false
     // binning path the host launches only as many passes as recent frames needed
     // (depth_budget, check_overflow); a frame that needs more is flagged by the
     // column scan and re-rendered with all four, like a pair-buffer overflow.
-    const int launch = with_rects && c->depth_skip ? std::max(1, std::min(4, c->depth_budget)) : 4;
+    const int launch = with_rects && c->set.depth_skip ? std::max(1, std::min(4, c->depth_budget)) : 4;
     c->passes_launched = launch;
     const gsr::SortFilter near{1, c->kcut, c->nlive, c->kcut_frame};
     for (int p = 0; p < launch; p++) {
@@ -1409,17 +1435,17 @@ static int depth_sort_locked(gsr_context* c, bool with_rects, bool plain = false
         HIP_TRY(gsr::launch_radix_pass(f0 ? c->src_items : c->items[p & 1], c->items[(p + 1) & 1],
                                        (part || (key && p > 0)) ? c->nlive : nullptr, n, 32 + 8 * p, 8,
                                        key && p > 0 ? gd_near : gd, di,
-                                       c->hist, c->totals, nullptr, c->stream, c->depth_skip ? c->dstats : nullptr,
-                                       p, with_rects ? reinterpret_cast<const uint32_t*>(c->rect) : nullptr, rect_mode,
+                                       c->hist, c->totals, nullptr, c->stream, c->set.depth_skip ? c->dstats : nullptr,
+                                       p, with_rects ? reinterpret_cast<const uint32_t*>(c->rect.get()) : nullptr, rect_mode,
                                        with_rects ? pay_buf(c, 0) : nullptr,
                                        with_rects ? pay_buf(c, 1) : nullptr, rank_atomic_on(c), nullptr, nullptr,
                                        f0 ? &near : nullptr));
     }
     // the bucket sort's first splitters: quantiles of this whole sorted order (the next
     // frame of this scene size is bucket-sorted)
-    if (with_rects && !key && c->bucket_sort && bkt_applies(c, c->n) && c->bkt_B != bkt_count(c, c->n)) {
+    if (with_rects && !key && c->set.bucket_sort && bkt_applies(c, c->n) && c->bkt_B != bkt_count(c, c->n)) {
         const int B = bkt_count(c, c->n);
-        HIP_TRY(gsr::launch_bkt_splitters(c->items[0], c->items[1], c->depth_skip ? c->dstats : nullptr, n,
+        HIP_TRY(gsr::launch_bkt_splitters(c->items[0], c->items[1], c->set.depth_skip ? c->dstats : nullptr, n,
                                           part ? c->nlive : nullptr, B,
                                           c->bkt_split + (size_t)c->bkt_par * gsr::kMaxBuckets, c->stream));
         c->bkt_B = B;
@@ -1432,13 +1458,13 @@ static int depth_sort_locked(gsr_context* c, bool with_rects, bool plain = false
 // pass plan), every kernel returning at once when phase A saturated every block.
 static int far_sort_locked(gsr_context* c) {
     const uint32_t n = (uint32_t)c->n;
-    const int di = c->depth_items ? c->depth_items : (c->n < (int64_t(4) << 20) ? 8 : 16);
+    const int di = c->set.depth_items ? c->set.depth_items : (c->n < (int64_t(4) << 20) ? 8 : 16);
     int gd = groups_for(c->n, 256 * di);
-    if (c->depth_groups) gd = std::min(gd, c->depth_groups);
+    if (c->set.depth_groups) gd = std::min(gd, c->set.depth_groups);
     // the pass budget follows the near sorts (phase A's column scan reports them, and
     // their key range can be far narrower); the far keys get at least three passes
     // (keys below 2^24, depths under 16.7), so a phase B is rarely short of passes
-    const int launch = c->depth_skip ? std::max(3, std::min(4, c->depth_budget)) : 4;
+    const int launch = c->set.depth_skip ? std::max(3, std::min(4, c->depth_budget)) : 4;
     c->far_launched = launch;
     // the summed-area table of the tiles phase A left unsaturated; pass 0 reads the whole
     // preprocess order and keeps the items with keys at or above the frame's threshold
@@ -1450,8 +1476,8 @@ static int far_sort_locked(gsr_context* c) {
     for (int p = 0; p < launch; p++)
         HIP_TRY(gsr::launch_radix_pass(p == 0 ? c->src_items : c->items[p & 1], c->items[(p + 1) & 1], nullptr, n,
                                        32 + 8 * p, 8, gd, di, c->hist, c->totals, nullptr, c->stream,
-                                       c->depth_skip ? c->dstats_far : nullptr, p,
-                                       reinterpret_cast<const uint32_t*>(c->rect), p == 0 ? 1 : 0, pay_buf(c, 0),
+                                       c->set.depth_skip ? c->dstats_far : nullptr, p,
+                                       reinterpret_cast<const uint32_t*>(c->rect.get()), p == 0 ? 1 : 0, pay_buf(c, 0),
                                        pay_buf(c, 1), rank_atomic_on(c), c->nlive, c->gate, p == 0 ? &far : &rest));
     return GSR_OK;
 }
@@ -1478,7 +1504,7 @@ static int bin_locked(gsr_context* c, uint32_t base, uint32_t count, int gate_mo
                       const gsr::RowSplit* rs = nullptr, bool far = false) {
     const uint32_t cap = (uint32_t)c->p_cap;
     if (int rc = ensure_cbins(c)) return rc;
-    auto* row_pairs = reinterpret_cast<unsigned long long*>(c->binmeta);
+    auto* row_pairs = reinterpret_cast<unsigned long long*>(c->binmeta.get());
     auto* row_items = reinterpret_cast<uint32_t*>(c->binmeta + 256);
     // key mode, phase A: about 2 x the split point's items (the count is on the device)
     const int64_t est = rs && rs->cut_mode == 1 ? std::min<int64_t>(count, std::max<int64_t>(2 * (int64_t)rs->na, 65536))
@@ -1490,25 +1516,25 @@ static int bin_locked(gsr_context* c, uint32_t base, uint32_t count, int gate_mo
     const int64_t row_chunk = !rs && est > kBucketSortMaxN ? 3072 : 1024;
     const int gb = std::min(groups_for(est, row_chunk), gsr::kMaxSortGroups / 2);
     // (a bucket-sorted frame has no pass plan: its order is in items[0], its rects in pay_buf 0)
-    uint32_t* dst = c->depth_skip && !(c->last_bds && !far) ? (far ? c->dstats_far : c->dstats) : nullptr;
+    uint32_t* dst = c->set.depth_skip && !(c->last_bds && !far) ? (far ? c->dstats_far : c->dstats) : nullptr;
     // after a bucket-sorted plain frame the buckets are the row chunks and their counts exist
     const bool fused = c->bkt_rows_fused && gate_mode == 0 && base == 0 && !rs && !far && count == (uint32_t)c->n;
     c->bkt_rows_fused = false;
     const uint32_t* cstart = fused ? c->totals + c->bkt_B : nullptr;
     HIP_TRY(gsr::launch_bin_rows(c->items[0], c->items[1], dst, count, pay_buf(c, 0),
                                  pay_buf(c, 1), fused ? c->bkt_B : gb,
-                                 c->hist, row_items, row_pairs, cap, c->fr.tiles_y, c->pairs[0], c->bin_row_items,
+                                 c->hist, row_items, row_pairs, cap, c->fr.tiles_y, c->pairs[0], c->set.bin_row_items,
                                  c->stream, c->spans_frame ? c->spans : nullptr, rank_atomic_on(c), base,
                                  gate_mode ? c->gate : nullptr, gate_mode, rs && rs->cut_mode ? c->nlive : nullptr,
                                  rs, cstart));
     if (marks) mark(c, GSR_STAGE_TILE_SORT);
     // column-pass workgroups: ~one 2048-item chunk each (config 3: 2048-4096 groups 12 us
     // faster than 1024; config 2: 1024 best, profiles/r02_ab_col_groups.txt)
-    const int gcol = c->bin_col_groups ? c->bin_col_groups
+    const int gcol = c->set.bin_col_groups ? c->set.bin_col_groups
                                        : (int)std::min<int64_t>(4096, std::max<int64_t>(1024, c->n / 1024));
     HIP_TRY(gsr::launch_bin_cols(c->pairs[0], row_items, row_pairs, c->cbins, gcol, cap,
                                  c->fr.tiles_x, c->fr.tiles_y, pair_vals(c, 1), c->ranges, c->stats,
-                                 c->hstats_dev, c->bin_col_items, c->stream,
+                                 c->hstats_dev, c->set.bin_col_items, c->stream,
                                  dst, far ? c->far_launched : c->passes_launched, rank_atomic_on(c),
                                  gate_mode == 2 ? c->gate : nullptr, c->fstatus, col_chunk_for(c)));
     c->pair_buf = 1;
@@ -1527,7 +1553,7 @@ static int sort_locked(gsr_context* c, bool allow_split) {
     // count mode sorts the whole order and phase A bins its nearest na positions; key
     // mode (a threshold from an earlier split frame exists) partitions by the threshold
     // and sorts only the near part, which phase A bins
-    const uint32_t na = (uint32_t)std::max<int64_t>(1, ((int64_t)n * c->split_pm + 999) / 1000);
+    const uint32_t na = (uint32_t)std::max<int64_t>(1, ((int64_t)n * c->ctl.split_pm + 999) / 1000);
     const bool split = bin && allow_split && split_enabled(c, c->n) && na < n;
     if (c->split_key && !split) {   // preprocessed for key mode: sort every visible item instead
         c->split_key = false;
@@ -1555,14 +1581,14 @@ static int sort_locked(gsr_context* c, bool allow_split) {
         c->frame_key = key;
         // speculate only when the camera is the one the threshold came from (a moving camera
         // would leave blocks unsaturated and cost a re-render)
-        const bool same_view = std::memcmp(c->split_view, c->fr.V, sizeof c->fr.V) == 0 &&
-                               std::memcmp(c->split_view + 16, c->fr.P, sizeof c->fr.P) == 0;
+        const bool same_view = std::memcmp(c->ctl.split_view, c->fr.V, sizeof c->fr.V) == 0 &&
+                               std::memcmp(c->ctl.split_view + 16, c->fr.P, sizeof c->fr.P) == 0;
         // (and only with completion events on: a captured graph would bake "no phase B"
         // into every replay)
-        c->frame_spec = split && key && c->split_spec && same_view && c->completion_events;
+        c->frame_spec = split && key && c->ctl.split_spec && same_view && c->set.completion_events;
         if (split) {
-            std::memcpy(c->split_view, c->fr.V, sizeof c->fr.V);
-            std::memcpy(c->split_view + 16, c->fr.P, sizeof c->fr.P);
+            std::memcpy(c->ctl.split_view, c->fr.V, sizeof c->fr.V);
+            std::memcpy(c->ctl.split_view + 16, c->fr.P, sizeof c->fr.P);
         }
         mark(c, GSR_STAGE_EMIT);
         if (split) {
@@ -1581,25 +1607,25 @@ static int sort_locked(gsr_context* c, bool allow_split) {
     mark(c, GSR_STAGE_EMIT);
     const int ge = groups_for(c->n, 1024);
     const bool key16 = c->ntiles <= 65536;
-    HIP_TRY(gsr::launch_emit(c->items[0], c->items[1], c->depth_skip ? c->dstats : nullptr, n, c->rect, ge, c->wg,
+    HIP_TRY(gsr::launch_emit(c->items[0], c->items[1], c->set.depth_skip ? c->dstats : nullptr, n, c->rect, ge, c->wg,
                              c->stats, c->hstats_dev, (uint32_t)c->p_cap, c->fr.tiles_x, c->fr.tiles_y,
                              pair_keys(c, 0), key16, pair_vals(c, 0), c->ranges, c->stream, c->fstatus));
     // ---- stable key-value tile sort ----
     mark(c, GSR_STAGE_TILE_SORT);
     const int tbits = std::max(1, ceil_log2(c->ntiles));
-    int gp = groups_for(c->p_cap, 256 * c->tile_items);
-    if (c->tile_groups) gp = std::min(gp, c->tile_groups);
+    int gp = groups_for(c->p_cap, 256 * c->set.tile_items);
+    if (c->set.tile_groups) gp = std::min(gp, c->set.tile_groups);
     int cur = 0;
     // digits split evenly over the passes (13 bits: 7 + 6, not 8 + 5): longer
     // digit runs per sorted tile of items, so the scattered stores coalesce better
     const int tpasses = (tbits + 7) / 8;
-    const int tdig = c->tile_split_even ? (tbits + tpasses - 1) / tpasses : 8;
+    const int tdig = c->set.tile_split_even ? (tbits + tpasses - 1) / tpasses : 8;
     for (int sh = 0; sh < tbits; sh += tdig) {
         const int bits = std::min(tdig, tbits - sh);
         const bool last = sh + tdig >= tbits;    // final pass: values only + tile ranges
         HIP_TRY(gsr::launch_kv_pass(pair_keys(c, cur), pair_vals(c, cur), last ? nullptr : pair_keys(c, cur ^ 1),
                                     pair_vals(c, cur ^ 1), key16, &c->stats[0].pairs_eff, sh, bits, gp,
-                                    c->tile_items, c->hist, c->totals, last ? c->ranges : nullptr, c->stream));
+                                    c->set.tile_items, c->hist, c->totals, last ? c->ranges : nullptr, c->stream));
         cur ^= 1;
     }
     c->pair_buf = cur;
@@ -1618,7 +1644,7 @@ static int blend_locked(gsr_context* c, float* d_out) {
         const int64_t need = c->blend_variant == 3 ? 12 * (int64_t)c->ntiles + 64   // >= 2 x the padded grid
                                                    : 16 + (int64_t)c->fr.W * c->fr.H;
         if (c->consumed_cap < need) {
-            if (int rc = realloc_dev(&c->consumed, (size_t)need)) return rc;
+            if (int rc = c->consumed.alloc((size_t)need)) return rc;
             c->consumed_cap = need;
         }
         HIP_TRY(hipMemsetAsync(c->consumed, 0, (size_t)need * sizeof(unsigned long long), c->stream));
@@ -1639,14 +1665,14 @@ static int blend_locked(gsr_context* c, float* d_out) {
             // phase A; its workgroup 0 also sets the next frame's threshold from the near
             // depth order (key mode: the near part; count mode: the whole order)
             const bool spec = c->frame_spec;
-            const gsr::SplitCut cut{c->items[0], c->items[1], c->depth_skip && !c->last_bds ? c->dstats : nullptr,
+            const gsr::SplitCut cut{c->items[0], c->items[1], c->set.depth_skip && !c->last_bds ? c->dstats : nullptr,
                                     key ? c->nlive : nullptr, n, c->split_na, c->split_rebin ? nullptr : c->kcut};
             gsr::BlendSplit a{1, c->tbuf, c->bflag, c->gate, nullptr, spec ? c->hstats_dev : nullptr, cut, 0u,
                               spec ? c->fstatus : nullptr};
             HIP_TRY(gsr::launch_blend(pair_vals(c, c->pair_buf), c->ranges, c->rec, c->fr, d_out,
-                                      c->diagnostics ? c->consumed : nullptr, false, c->blend_band_tiles, 0,
+                                      c->diagnostics ? c->consumed : nullptr, false, c->set.blend_band_tiles, 0,
                                       c->stream, &a));
-            c->split_key_ready = true;
+            c->ctl.split_key_ready = true;
             mark(c, GSR_STAGE_RESUME);
             if (!spec) {
                 // phase B: (key mode) sort the far part, then bin the rest of the order
@@ -1662,9 +1688,9 @@ static int blend_locked(gsr_context* c, float* d_out) {
                 gsr::BlendSplit b{2, c->tbuf, c->bflag, c->gate, c->hstats_dev, nullptr, bcut, split_tag(c),
                                   nullptr};
                 HIP_TRY(gsr::launch_blend(pair_vals(c, c->pair_buf), c->ranges, c->rec, c->fr, d_out,
-                                          c->diagnostics ? c->consumed : nullptr, false, c->blend_band_tiles, 0,
+                                          c->diagnostics ? c->consumed : nullptr, false, c->set.blend_band_tiles, 0,
                                           c->stream, &b));
-                c->split_seen = true;
+                c->ctl.split_seen = true;
             }
             c->split_rebin = true;
         } else {
@@ -1673,12 +1699,12 @@ static int blend_locked(gsr_context* c, float* d_out) {
             c->split_frame = false;
             HIP_TRY(gsr::launch_blend(pair_vals(c, c->pair_buf), c->ranges, c->rec, c->fr, d_out,
                                       c->diagnostics ? c->consumed : nullptr, c->blend_variant == 3,
-                                      c->blend_band_tiles, c->blend_exp, c->stream));
+                                      c->set.blend_band_tiles, c->set.blend_exp, c->stream));
         }
     } else {
         HIP_TRY(gsr::launch_blend(pair_vals(c, c->pair_buf), c->ranges, c->rec, c->fr, d_out,
                                   c->diagnostics ? c->consumed : nullptr, c->blend_variant == 3,
-                                  c->blend_band_tiles, c->blend_exp, c->stream));
+                                  c->set.blend_band_tiles, c->set.blend_exp, c->stream));
     }
     mark(c, GSR_NUM_STAGES);
     if (c->timing && c->timing_now) c->ev_frames.push_back(c->cur);
@@ -1687,7 +1713,7 @@ static int blend_locked(gsr_context* c, float* d_out) {
     // frames skip the record (~3 us each). The overflow stats are sticky, so reading
     // them when that older frame completes still sees every overflow so far, and
     // gsr_sync drains the stream before it reads them.
-    if (!c->pending && c->completion_events) {
+    if (!c->pending && c->set.completion_events) {
         HIP_TRY(hipEventRecord(c->done_ev, c->stream));
         c->pending = true;
     }
@@ -1730,51 +1756,12 @@ extern "C" int gsr_render(gsr_context* c, const void* scene, int layout, int64_t
 
 namespace {
 
-// The depth split's controller: what check_overflow and the preprocess adapt from frame to
-// frame.  An aux frame takes no part in it (gsr_render_aux saves and restores it).
-struct SplitCtl {
-    int split_pm, split_floor, split_clean, split_off_frames, split_retry;
-    uint32_t split_epoch;
-    bool split_seen, split_spec, split_key_ready;
-    float split_off_view[32], prev_view[32], split_view[32];
-};
-
-void split_ctl_save(const gsr_context* c, SplitCtl* s) {
-    s->split_pm = c->split_pm;
-    s->split_floor = c->split_floor;
-    s->split_clean = c->split_clean;
-    s->split_off_frames = c->split_off_frames;
-    s->split_retry = c->split_retry;
-    s->split_epoch = c->split_epoch;
-    s->split_seen = c->split_seen;
-    s->split_spec = c->split_spec;
-    s->split_key_ready = c->split_key_ready;
-    std::memcpy(s->split_off_view, c->split_off_view, sizeof s->split_off_view);
-    std::memcpy(s->prev_view, c->prev_view, sizeof s->prev_view);
-    std::memcpy(s->split_view, c->split_view, sizeof s->split_view);
-}
-
-void split_ctl_restore(gsr_context* c, const SplitCtl& s) {
-    c->split_pm = s.split_pm;
-    c->split_floor = s.split_floor;
-    c->split_clean = s.split_clean;
-    c->split_off_frames = s.split_off_frames;
-    c->split_retry = s.split_retry;
-    c->split_epoch = s.split_epoch;
-    c->split_seen = s.split_seen;
-    c->split_spec = s.split_spec;
-    c->split_key_ready = s.split_key_ready;
-    std::memcpy(c->split_off_view, s.split_off_view, sizeof s.split_off_view);
-    std::memcpy(c->prev_view, s.prev_view, sizeof s.prev_view);
-    std::memcpy(c->split_view, s.split_view, sizeof s.split_view);
-}
-
 // The aux frame's -Z array (n floats), grown like the other per-Gaussian buffers.
 int ensure_aux_z(gsr_context* c, int64_t n) {
     if (n <= c->aux_z_cap) return GSR_OK;
     const int64_t cap = std::max<int64_t>(n, 1024);
     HIP_TRY(hipDeviceSynchronize());
-    if (int rc = realloc_dev(&c->aux_z, (size_t)cap)) return rc;
+    if (int rc = c->aux_z.alloc((size_t)cap)) return rc;
     c->aux_z_cap = cap;
     return GSR_OK;
 }
@@ -1784,7 +1771,7 @@ int ensure_aux_pack(gsr_context* c, int64_t n) {
     if (n <= c->aux_pack_cap) return GSR_OK;
     const int64_t cap = std::max<int64_t>(n, 1024);
     HIP_TRY(hipDeviceSynchronize());
-    if (int rc = realloc_dev(&c->aux_pack, 2 * (size_t)cap)) return rc;
+    if (int rc = c->aux_pack.alloc(2 * (size_t)cap)) return rc;
     c->aux_pack_cap = cap;
     return GSR_OK;
 }
@@ -1794,7 +1781,7 @@ int blend_aux_done(gsr_context* c) {
     mark(c, GSR_NUM_STAGES);
     if (c->timing && c->timing_now) c->ev_frames.push_back(c->cur);
     c->cur = FrameEvents{};
-    if (!c->pending && c->completion_events) {
+    if (!c->pending && c->set.completion_events) {
         HIP_TRY(hipEventRecord(c->done_ev, c->stream));
         c->pending = true;
     }
@@ -1817,7 +1804,7 @@ int blend_aux_locked(gsr_context* c, float* d_out, const gsr_aux_targets& aux) {
                                       c->pre_layout == GSR_LAYOUT_SCENE_BLOCK_4D, c->time, c->aux_z, c->stream));
     HIP_TRY(gsr::launch_blend_aux(pair_vals(c, c->pair_buf), c->ranges, c->rec, c->fr, d_out, aux.d_alpha,
                                   aux.d_depth, c->aux_z, aux.d_features, c->n, aux.nfeat, aux.d_feat_out, c->aux_pack,
-                                  c->blend_band_tiles, c->stream));
+                                  c->set.blend_band_tiles, c->stream));
     return blend_aux_done(c);
 }
 
@@ -1828,7 +1815,7 @@ int blend_contrib_locked(gsr_context* c, const gsr_contrib_targets& out) {
     mark(c, GSR_STAGE_BLEND);
     HIP_TRY(gsr::launch_blend_contrib(pair_vals(c, c->pair_buf), c->ranges, c->rec, c->fr, out.d_count,
                                       reinterpret_cast<unsigned long long*>(out.d_weight), out.d_max, out.d_id,
-                                      &c->stats[0].overflow, c->blend_band_tiles, c->stream));
+                                      &c->stats[0].overflow, c->set.blend_band_tiles, c->stream));
     return blend_aux_done(c);
 }
 
@@ -1838,7 +1825,7 @@ int blend_backward_locked(gsr_context* c, const gsr_backward_targets& bw) {
     mark(c, GSR_STAGE_BLEND);
     HIP_TRY(gsr::launch_blend_backward(pair_vals(c, c->pair_buf), c->ranges, c->rec, c->fr, bw.d_grad_image,
                                        bw.d_grad_alpha, bw.d_color, bw.d_opacity, bw.d_conic, bw.d_center, c->n,
-                                       &c->stats[0].overflow, c->blend_band_tiles, c->stream));
+                                       &c->stats[0].overflow, c->set.blend_band_tiles, c->stream));
     return blend_aux_done(c);
 }
 
@@ -1852,11 +1839,10 @@ int blend_backward_locked(gsr_context* c, const gsr_backward_targets& bw) {
 template <typename Blend>
 int aux_frame_locked(gsr_context* c, const void* scene, int layout, int64_t n, const gsr_camera* cam, int W, int H,
                      int nx, int ny, int ws, int hs, float k, void* stream, Blend&& blend) {
-    SplitCtl ctl;
-    split_ctl_save(c, &ctl);
+    SplitCtl ctl = c->ctl;
     const int state = split_state(c);
-    const int depth_split = c->depth_split;
-    c->depth_split = 0;
+    const int depth_split = c->set.depth_split;
+    c->set.depth_split = 0;
     int rc = preprocess_locked(c, scene, layout, n, cam, W, H, nx, ny, ws, hs, k, stream);
     int r2 = GSR_OK;
     if (rc == GSR_OK || rc == GSR_E_OVERFLOW) {
@@ -1864,16 +1850,16 @@ int aux_frame_locked(gsr_context* c, const void* scene, int layout, int64_t n, c
         if (r2 == GSR_OK) r2 = blend();
         c->split_state_hold = state;
     }
-    c->depth_split = depth_split;
+    c->set.depth_split = depth_split;
     if (rc == GSR_E_OVERFLOW) {
         // the view bookkeeping only
-        ctl.split_pm = c->split_pm;
-        ctl.split_floor = c->split_floor;
-        ctl.split_clean = c->split_clean;
-        ctl.split_spec = c->split_spec;
-        ctl.split_seen = c->split_seen;
+        ctl.split_pm = c->ctl.split_pm;
+        ctl.split_floor = c->ctl.split_floor;
+        ctl.split_clean = c->ctl.split_clean;
+        ctl.split_spec = c->ctl.split_spec;
+        ctl.split_seen = c->ctl.split_seen;
     }
-    split_ctl_restore(c, ctl);
+    c->ctl = ctl;
     if (rc != GSR_OK && rc != GSR_E_OVERFLOW) return rc;
     return r2 ? r2 : rc;
 }
@@ -1952,7 +1938,7 @@ int ensure_rec_grads(gsr_context* c, int64_t n) {
     if (10 * n <= c->rec_grads_cap) return GSR_OK;
     const int64_t cap = 10 * std::max<int64_t>(n, 1024);
     HIP_TRY(hipDeviceSynchronize());
-    if (int rc = realloc_dev(&c->rec_grads, (size_t)cap)) return rc;
+    if (int rc = c->rec_grads.alloc((size_t)cap)) return rc;
     c->rec_grads_cap = cap;
     return GSR_OK;
 }
@@ -2008,30 +1994,9 @@ extern "C" int gsr_render_backward_scene(gsr_context* c, const void* scene, int 
 
 namespace {
 
-// Everything that selects kernels or schedules (all settings are bit-identical);
-// diagnostics and timing stay on lane 0 only.
-void copy_settings(gsr_context* d, const gsr_context* s) {
-    d->tile_items = s->tile_items;
-    d->depth_items = s->depth_items;
-    d->bucket_sort = s->bucket_sort;
-    d->fuse_rows = s->fuse_rows;
-    d->col_chunk = s->col_chunk;
-    d->tile_groups = s->tile_groups;
-    d->tile_split_even = s->tile_split_even;
-    d->depth_skip = s->depth_skip;
-    d->depth_groups = s->depth_groups;
-    d->tile_binning = s->tile_binning;
-    d->bin_row_items = s->bin_row_items;
-    d->bin_col_items = s->bin_col_items;
-    d->tile_spans = s->tile_spans;
-    d->bin_col_groups = s->bin_col_groups;
-    d->blend_band_tiles = s->blend_band_tiles;
-    d->blend_exp = s->blend_exp;
-    d->depth_split = s->depth_split;   // the split point adapts per lane (set at creation and by the knob)
-    d->completion_events = s->completion_events;
-    d->depth_compact = s->depth_compact;
-    d->rank_atomic = s->rank_atomic;
-}
+// What a lane inherits from lane 0: the settings; diagnostics and timing stay on lane 0 only,
+// and the split point adapts per lane (set at creation and by the knob).
+void copy_settings(gsr_context* d, const gsr_context* s) { d->set = s->set; }
 
 // Lanes 1..F-1: child contexts, streams and events, created once and kept.
 int ensure_lanes(gsr_context* c, int F) {
@@ -2040,8 +2005,8 @@ int ensure_lanes(gsr_context* c, int F) {
     while ((int)c->lanes.size() < F - 1) {
         gsr_context* l = new gsr_context();
         l->inflight = 1;
-        l->split_pm = c->split_pm;
-        l->split_floor = c->split_floor;
+        l->ctl.split_pm = c->ctl.split_pm;
+        l->ctl.split_floor = c->ctl.split_floor;
         hipStream_t s = nullptr;
         hipEvent_t e = nullptr;
         if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess ||
@@ -2068,10 +2033,10 @@ int ensure_alt(gsr_context* c) {
     if (!c->alt_ev) HIP_TRY(hipEventCreateWithFlags(&c->alt_ev, hipEventDisableTiming));
     if (c->alt_cap >= c->n_cap) return GSR_OK;
     HIP_TRY(hipDeviceSynchronize());
-    if (int rc = realloc_dev(&c->alt_rec, 4 * (size_t)c->n_cap)) return rc;
-    if (int rc = realloc_dev(&c->alt_items, (size_t)c->n_cap)) return rc;
-    if (int rc = realloc_dev(&c->alt_rect, (size_t)c->n_cap)) return rc;
-    if (int rc = realloc_dev(&c->alt_spans, (size_t)c->n_cap)) return rc;
+    if (int rc = c->alt_rec.alloc(4 * (size_t)c->n_cap)) return rc;
+    if (int rc = c->alt_items.alloc((size_t)c->n_cap)) return rc;
+    if (int rc = c->alt_rect.alloc((size_t)c->n_cap)) return rc;
+    if (int rc = c->alt_spans.alloc((size_t)c->n_cap)) return rc;
     c->alt_cap = c->n_cap;
     return GSR_OK;
 }
@@ -2476,7 +2441,7 @@ static int depth_passes_locked(gsr_context* c, int* passes) {
         *passes = 0;
         return GSR_OK;
     }
-    if (!c->depth_skip) return GSR_OK;
+    if (!c->set.depth_skip) return GSR_OK;
     uint32_t st[4];   // same plan as the kernels (gsr_device.h depth_pass_skipped)
     HIP_TRY(hipMemcpy(st, c->dstats, sizeof st, hipMemcpyDeviceToHost));
     int p = 1;
@@ -2642,36 +2607,85 @@ extern "C" int gsr_set_time(gsr_context* c, float t) {
     return GSR_OK;
 }
 
+namespace {
+
+// One row per knob that is a stored value: where it lives (a Settings field, which lanes
+// inherit, or a field of the context, which is lane 0's alone), the values gsr_set_tuning
+// accepts, and what it says when it refuses one.  The read-only knobs, the split point and
+// GSR_TUNE_RANK_ATOMIC's read are spelled out in the two functions below.
+struct Knob {
+    enum Accept { kOneOf, kRange, kBool };   // v[0 .. nv) | v[0] .. v[1] inclusive | any, stored as != 0
+    int id;
+    int Settings::*set;
+    int gsr_context::*ctx;
+    Accept accept;
+    int nv;
+    int v[4];
+    const char* refusal;
+
+    int& at(gsr_context* c) const { return set ? c->set.*set : c->*ctx; }
+    bool accepts(int x) const {
+        if (accept == kRange) return x >= v[0] && x <= v[1];
+        return accept == kBool || std::find(v, v + nv, x) != v + nv;
+    }
+};
+
+constexpr const char* kBinItemsMsg = "binning items per thread must be 4, 8 or 16";
+constexpr Knob kKnobs[] = {
+    {GSR_TUNE_BLEND_SCHEDULE, nullptr, &gsr_context::blend_variant, Knob::kOneOf, 2, {0, 3},
+     "blend schedule must be 0 (default) or 3 (timeline stamps)"},
+    {GSR_TUNE_TILE_SORT_ITEMS, &Settings::tile_items, nullptr, Knob::kOneOf, 2, {8, 16},
+     "tile-sort items must be 8 or 16"},
+    {GSR_TUNE_DEPTH_SORT_ITEMS, &Settings::depth_items, nullptr, Knob::kOneOf, 4, {0, 4, 8, 16},
+     "depth-sort items must be 0, 4, 8 or 16"},
+    {GSR_TUNE_TILE_SORT_GROUPS, &Settings::tile_groups, nullptr, Knob::kRange, 2, {0, gsr::kMaxSortGroups},
+     "bad group cap"},
+    {GSR_TUNE_DEPTH_SORT_GROUPS, &Settings::depth_groups, nullptr, Knob::kRange, 2, {0, gsr::kMaxSortGroups},
+     "bad group cap"},
+    {GSR_TUNE_TILE_SORT_SPLIT, &Settings::tile_split_even, nullptr, Knob::kBool, 0, {}, nullptr},
+    {GSR_TUNE_DEPTH_SORT_SKIP, &Settings::depth_skip, nullptr, Knob::kBool, 0, {}, nullptr},
+    {GSR_TUNE_TILE_BINNING, &Settings::tile_binning, nullptr, Knob::kBool, 0, {}, nullptr},
+    {GSR_TUNE_BIN_ROW_ITEMS, &Settings::bin_row_items, nullptr, Knob::kOneOf, 3, {4, 8, 16}, kBinItemsMsg},
+    {GSR_TUNE_BIN_COL_ITEMS, &Settings::bin_col_items, nullptr, Knob::kOneOf, 3, {4, 8, 16}, kBinItemsMsg},
+    {GSR_TUNE_BIN_COL_GROUPS, &Settings::bin_col_groups, nullptr, Knob::kRange, 2, {0, 65536},
+     "bad column-pass group count"},
+    {GSR_TUNE_COMPLETION_EVENTS, &Settings::completion_events, nullptr, Knob::kBool, 0, {}, nullptr},
+    {GSR_TUNE_BLEND_BAND_TILES, &Settings::blend_band_tiles, nullptr, Knob::kRange, 2, {0, 65536},
+     "blend band tiles must be 0..65536"},
+    {GSR_TUNE_DEPTH_COMPACT, &Settings::depth_compact, nullptr, Knob::kRange, 2, {0, 2},
+     "depth compaction must be 0, 1 or 2"},
+    {GSR_TUNE_TILE_SPANS, &Settings::tile_spans, nullptr, Knob::kRange, 2, {0, 2}, "tile spans must be 0, 1 or 2"},
+    {GSR_TUNE_RANK_ATOMIC, &Settings::rank_atomic, nullptr, Knob::kRange, 2, {0, 1}, "rank path must be 0 or 1"},
+    {GSR_TUNE_BLEND_EXP, &Settings::blend_exp, nullptr, Knob::kRange, 2, {0, 2}, "blend exp must be 0, 1 or 2"},
+    {GSR_TUNE_DEPTH_SPLIT, &Settings::depth_split, nullptr, Knob::kRange, 2, {0, 2}, "depth split must be 0, 1 or 2"},
+    {GSR_TUNE_DEPTH_BUCKETS, &Settings::bucket_sort, nullptr, Knob::kRange, 2, {0, 3}, "depth buckets must be 0..3"},
+    {GSR_TUNE_BUCKET_ROWS, &Settings::fuse_rows, nullptr, Knob::kBool, 0, {}, nullptr},
+    {GSR_TUNE_COL_CHUNK, &Settings::col_chunk, nullptr, Knob::kOneOf, 3, {0, 1024, 2048},
+     "column chunk must be 0, 1024 or 2048"},
+    {GSR_TUNE_FAIL_FRAME, nullptr, &gsr_context::fail_frame, Knob::kRange, 2, {0, INT32_MAX},
+     "fail frame must be >= 0"},
+    {GSR_TUNE_PATH_SHARED_PRE, nullptr, &gsr_context::path_shared_pre, Knob::kRange, 2, {0, 1},
+     "shared preprocess must be 0 or 1"},
+};
+
+const Knob* find_knob(int id) {
+    for (const Knob& k : kKnobs)
+        if (k.id == id) return &k;
+    return nullptr;
+}
+
+}  // namespace
+
 extern "C" int gsr_get_tuning(gsr_context* c, int knob, int* value) {
     if (!c || !value) return set_err(GSR_E_ARG, "gsr_get_tuning: null argument");
     std::lock_guard<std::mutex> lk(c->mu);
-    switch (knob) {
-    case GSR_TUNE_BLEND_SCHEDULE: *value = c->blend_variant; break;
-    case GSR_TUNE_TILE_SORT_ITEMS: *value = c->tile_items; break;
-    case GSR_TUNE_DEPTH_SORT_ITEMS: *value = c->depth_items; break;
-    case GSR_TUNE_TILE_SORT_GROUPS: *value = c->tile_groups; break;
-    case GSR_TUNE_DEPTH_SORT_GROUPS: *value = c->depth_groups; break;
-    case GSR_TUNE_TILE_SORT_SPLIT: *value = c->tile_split_even ? 1 : 0; break;
-    case GSR_TUNE_DEPTH_SORT_SKIP: *value = c->depth_skip ? 1 : 0; break;
-    case GSR_TUNE_TILE_BINNING: *value = c->tile_binning; break;
-    case GSR_TUNE_BIN_ROW_ITEMS: *value = c->bin_row_items; break;
-    case GSR_TUNE_BIN_COL_ITEMS: *value = c->bin_col_items; break;
-    case GSR_TUNE_BIN_COL_GROUPS: *value = c->bin_col_groups; break;
-    case GSR_TUNE_COMPLETION_EVENTS: *value = c->completion_events ? 1 : 0; break;
-    case GSR_TUNE_BLEND_BAND_TILES: *value = c->blend_band_tiles; break;
-    case GSR_TUNE_DEPTH_COMPACT: *value = c->depth_compact; break;
-    case GSR_TUNE_TILE_SPANS: *value = c->tile_spans; break;
-    case GSR_TUNE_BLEND_EXP: *value = c->blend_exp; break;
-    case GSR_TUNE_DEPTH_SPLIT: *value = c->depth_split; break;
-    case GSR_TUNE_DEPTH_SPLIT_PERMILLE: *value = c->split_pm; break;
-    case GSR_TUNE_DEPTH_SPLIT_UNSAT: *value = c->hstats ? (int)((const volatile Stats*)c->hstats)->split_unsat : 0; break;
-    case GSR_TUNE_DEPTH_SPLIT_STATE: *value = split_state(c); break;
-    case GSR_TUNE_DEPTH_BUCKETS: *value = c->bucket_sort; break;
-    case GSR_TUNE_BUCKET_ROWS: *value = c->fuse_rows; break;
-    case GSR_TUNE_COL_CHUNK: *value = c->col_chunk; break;
-    case GSR_TUNE_FAIL_FRAME: *value = c->fail_frame; break;
-    case GSR_TUNE_PATH_SHARED_PRE: *value = c->path_shared_pre; break;
-    case GSR_TUNE_PATH_SHARED_LAUNCHES: *value = (int)std::min<int64_t>(c->shared_launches, INT32_MAX); break;
+    switch (knob) {   // the knobs that are not a stored value read as it stands
+    case GSR_TUNE_DEPTH_SPLIT_PERMILLE: *value = c->ctl.split_pm; return GSR_OK;
+    case GSR_TUNE_DEPTH_SPLIT_UNSAT:
+        *value = c->hstats ? (int)((const volatile Stats*)c->hstats)->split_unsat : 0;
+        return GSR_OK;
+    case GSR_TUNE_DEPTH_SPLIT_STATE: *value = split_state(c); return GSR_OK;
+    case GSR_TUNE_PATH_SHARED_LAUNCHES: *value = (int)std::min<int64_t>(c->shared_launches, INT32_MAX); return GSR_OK;
     case GSR_TUNE_DEPTH_BUCKETS_OVER:
     case GSR_TUNE_DEPTH_BUCKETS_WORK: {
         auto get = [&](const gsr_context* x) -> int64_t {
@@ -2682,18 +2696,22 @@ extern "C" int gsr_get_tuning(gsr_context* c, int knob, int* value) {
         int64_t v = get(c);
         for (auto* l : c->lanes) v += get(l);
         *value = (int)std::min<int64_t>(v, INT32_MAX);
-        break;
+        return GSR_OK;
     }
-    case GSR_TUNE_RANK_ATOMIC: *value = c->rank_atomic < 0 ? default_rank_atomic() : c->rank_atomic; break;
+    case GSR_TUNE_RANK_ATOMIC:   // not yet set: the environment's default
+        *value = c->set.rank_atomic < 0 ? default_rank_atomic() : c->set.rank_atomic;
+        return GSR_OK;
     case GSR_TUNE_RANK_ATOMIC_ACTIVE: {
         RankCheck rk;
         if (int rc = rank_check_device(&rk)) return rc;
-        const int asked = c->rank_atomic < 0 ? default_rank_atomic() : c->rank_atomic;
+        const int asked = c->set.rank_atomic < 0 ? default_rank_atomic() : c->set.rank_atomic;
         *value = asked > 0 && rk.state == 1 ? 1 : 0;
-        break;
+        return GSR_OK;
     }
-    default: return set_err(GSR_E_ARG, "gsr_get_tuning: unknown knob");
     }
+    const Knob* k = find_knob(knob);
+    if (!k) return set_err(GSR_E_ARG, "gsr_get_tuning: unknown knob");
+    *value = k->at(c);
     return GSR_OK;
 }
 
@@ -2701,104 +2719,6 @@ extern "C" int gsr_set_tuning(gsr_context* c, int knob, int value) {
     if (!c) return set_err(GSR_E_ARG, "null context");
     std::lock_guard<std::mutex> lk(c->mu);
     switch (knob) {
-    case GSR_TUNE_BLEND_SCHEDULE:
-        if (value != 0 && value != 3)
-            return set_err(GSR_E_ARG, "gsr_set_tuning: blend schedule must be 0 (default) or 3 (timeline stamps)");
-        c->blend_variant = value;
-        return GSR_OK;
-    case GSR_TUNE_TILE_SORT_ITEMS:
-        if (value != 8 && value != 16) return set_err(GSR_E_ARG, "gsr_set_tuning: tile-sort items must be 8 or 16");
-        c->tile_items = value;
-        return GSR_OK;
-    case GSR_TUNE_DEPTH_SORT_ITEMS:
-        if (value != 0 && value != 4 && value != 8 && value != 16)
-            return set_err(GSR_E_ARG, "gsr_set_tuning: depth-sort items must be 0, 4, 8 or 16");
-        c->depth_items = value;
-        return GSR_OK;
-    case GSR_TUNE_TILE_BINNING:
-        c->tile_binning = value != 0;
-        return GSR_OK;
-    case GSR_TUNE_BIN_ROW_ITEMS:
-    case GSR_TUNE_BIN_COL_ITEMS:
-        if (value != 4 && value != 8 && value != 16)
-            return set_err(GSR_E_ARG, "gsr_set_tuning: binning items per thread must be 4, 8 or 16");
-        (knob == GSR_TUNE_BIN_ROW_ITEMS ? c->bin_row_items : c->bin_col_items) = value;
-        return GSR_OK;
-    case GSR_TUNE_BLEND_BAND_TILES:
-        if (value < 0 || value > 65536) return set_err(GSR_E_ARG, "gsr_set_tuning: blend band tiles must be 0..65536");
-        c->blend_band_tiles = value;
-        return GSR_OK;
-    case GSR_TUNE_COMPLETION_EVENTS:
-        c->completion_events = value != 0;
-        return GSR_OK;
-    case GSR_TUNE_BIN_COL_GROUPS:
-        if (value < 0 || value > 65536) return set_err(GSR_E_ARG, "gsr_set_tuning: bad column-pass group count");
-        c->bin_col_groups = value;
-        return GSR_OK;
-    case GSR_TUNE_DEPTH_COMPACT:
-        if (value < 0 || value > 2) return set_err(GSR_E_ARG, "gsr_set_tuning: depth compaction must be 0, 1 or 2");
-        c->depth_compact = value;
-        return GSR_OK;
-    case GSR_TUNE_DEPTH_SORT_SKIP:
-        c->depth_skip = value != 0;
-        return GSR_OK;
-    case GSR_TUNE_TILE_SPANS:
-        if (value < 0 || value > 2) return set_err(GSR_E_ARG, "gsr_set_tuning: tile spans must be 0, 1 or 2");
-        c->tile_spans = value;
-        return GSR_OK;
-    case GSR_TUNE_TILE_SORT_SPLIT:
-        c->tile_split_even = value != 0;
-        return GSR_OK;
-    case GSR_TUNE_BLEND_EXP:
-        if (value < 0 || value > 2) return set_err(GSR_E_ARG, "gsr_set_tuning: blend exp must be 0, 1 or 2");
-        c->blend_exp = value;
-        return GSR_OK;
-    case GSR_TUNE_DEPTH_SPLIT:
-        if (value < 0 || value > 2) return set_err(GSR_E_ARG, "gsr_set_tuning: depth split must be 0, 1 or 2");
-        c->depth_split = value;
-        // the next split frame sorts the whole order (count mode), queues phase B
-        c->split_key_ready = c->split_spec = false;
-        for (auto* l : c->lanes) l->split_key_ready = l->split_spec = false;
-        return GSR_OK;
-    case GSR_TUNE_DEPTH_SPLIT_PERMILLE:
-        if (value < 1 || value > 999) return set_err(GSR_E_ARG, "gsr_set_tuning: split point must be 1..999");
-    {
-        auto restart = [value](gsr_context* x) {   // a new starting point for every lane
-            x->split_pm = value;
-            x->split_epoch++;
-            x->split_floor = 0;
-            x->split_clean = 0;
-            x->split_spec = false;
-            x->split_key_ready = false;
-        };
-        restart(c);
-        for (auto* l : c->lanes) restart(l);
-        return GSR_OK;
-    }
-    case GSR_TUNE_RANK_ATOMIC:
-        if (value != 0 && value != 1) return set_err(GSR_E_ARG, "gsr_set_tuning: rank path must be 0 or 1");
-        c->rank_atomic = value;
-        return GSR_OK;
-    case GSR_TUNE_DEPTH_BUCKETS:
-        if (value < 0 || value > 3) return set_err(GSR_E_ARG, "gsr_set_tuning: depth buckets must be 0..3");
-        c->bucket_sort = value;
-        return GSR_OK;
-    case GSR_TUNE_COL_CHUNK:
-        if (value != 0 && value != 1024 && value != 2048)
-            return set_err(GSR_E_ARG, "gsr_set_tuning: column chunk must be 0, 1024 or 2048");
-        c->col_chunk = value;
-        return GSR_OK;
-    case GSR_TUNE_BUCKET_ROWS:
-        c->fuse_rows = value != 0;
-        return GSR_OK;
-    case GSR_TUNE_FAIL_FRAME:
-        if (value < 0) return set_err(GSR_E_ARG, "gsr_set_tuning: fail frame must be >= 0");
-        c->fail_frame = value;
-        return GSR_OK;
-    case GSR_TUNE_PATH_SHARED_PRE:
-        if (value != 0 && value != 1) return set_err(GSR_E_ARG, "gsr_set_tuning: shared preprocess must be 0 or 1");
-        c->path_shared_pre = value;
-        return GSR_OK;
     case GSR_TUNE_RANK_ATOMIC_ACTIVE:
     case GSR_TUNE_DEPTH_SPLIT_UNSAT:
     case GSR_TUNE_DEPTH_SPLIT_STATE:
@@ -2806,14 +2726,31 @@ extern "C" int gsr_set_tuning(gsr_context* c, int knob, int value) {
     case GSR_TUNE_DEPTH_BUCKETS_WORK:
     case GSR_TUNE_PATH_SHARED_LAUNCHES:
         return set_err(GSR_E_ARG, "gsr_set_tuning: knob %d is read-only", knob);
-    case GSR_TUNE_TILE_SORT_GROUPS:
-    case GSR_TUNE_DEPTH_SORT_GROUPS:
-        if (value < 0 || value > gsr::kMaxSortGroups) return set_err(GSR_E_ARG, "gsr_set_tuning: bad group cap");
-        (knob == GSR_TUNE_TILE_SORT_GROUPS ? c->tile_groups : c->depth_groups) = value;
+    case GSR_TUNE_DEPTH_SPLIT_PERMILLE: {
+        if (value < 1 || value > 999) return set_err(GSR_E_ARG, "gsr_set_tuning: split point must be 1..999");
+        auto restart = [value](gsr_context* x) {   // a new starting point for every lane
+            x->ctl.split_pm = value;
+            x->ctl.split_epoch++;
+            x->ctl.split_floor = 0;
+            x->ctl.split_clean = 0;
+            x->ctl.split_spec = false;
+            x->ctl.split_key_ready = false;
+        };
+        restart(c);
+        for (auto* l : c->lanes) restart(l);
         return GSR_OK;
-    default:
-        return set_err(GSR_E_ARG, "gsr_set_tuning: unknown knob");
     }
+    }
+    const Knob* k = find_knob(knob);
+    if (!k) return set_err(GSR_E_ARG, "gsr_set_tuning: unknown knob");
+    if (!k->accepts(value)) return set_err(GSR_E_ARG, "gsr_set_tuning: %s", k->refusal);
+    k->at(c) = k->accept == Knob::kBool ? value != 0 : value;
+    if (knob == GSR_TUNE_DEPTH_SPLIT) {
+        // the next split frame sorts the whole order (count mode), queues phase B
+        c->ctl.split_key_ready = c->ctl.split_spec = false;
+        for (auto* l : c->lanes) l->ctl.split_key_ready = l->ctl.split_spec = false;
+    }
+    return GSR_OK;
 }
 
 extern "C" int gsr_rank_order_check(int64_t* lane_ops, int64_t* mismatches) {
@@ -2884,14 +2821,12 @@ extern "C" int gsr_blend_counters(gsr_context* c, int64_t* out4) {
 
 extern "C" int gsr_math_probe(const float* host_in, int n, float* host_out) {
     if (!host_in || !host_out || n <= 0) return set_err(GSR_E_ARG, "gsr_math_probe: bad argument");
-    float *din = nullptr, *dout = nullptr;
-    HIP_TRY(hipMalloc(&din, sizeof(float) * 2 * (size_t)n));
-    HIP_TRY(hipMalloc(&dout, sizeof(float) * 9 * (size_t)n));
+    DevBuf<float> din, dout;
+    if (int rc = din.alloc(2 * (size_t)n)) return rc;
+    if (int rc = dout.alloc(9 * (size_t)n)) return rc;
     HIP_TRY(hipMemcpy(din, host_in, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice));
     HIP_TRY(gsr::launch_math_probe(din, n, dout, nullptr));
     HIP_TRY(hipMemcpy(host_out, dout, sizeof(float) * 9 * (size_t)n, hipMemcpyDeviceToHost));
-    (void)hipFree(din);
-    (void)hipFree(dout);
     return GSR_OK;
 }
 
@@ -2899,10 +2834,10 @@ extern "C" int gsr_exp_probe2(float x_lo, float x_hi, float x_big, int64_t* viol
                               int64_t* packed_mismatches, float* err_all, float* err_big) {
     if (!violations || !packed_mismatches || !err_all || !err_big || !(x_lo < x_hi))
         return set_err(GSR_E_ARG, "gsr_exp_probe: bad argument");
-    unsigned long long* dv = nullptr;
-    uint32_t* de = nullptr;
-    HIP_TRY(hipMalloc(&dv, 2 * sizeof(unsigned long long)));
-    HIP_TRY(hipMalloc(&de, 2 * sizeof(uint32_t)));
+    DevBuf<unsigned long long> dv;
+    DevBuf<uint32_t> de;
+    if (int rc = dv.alloc(2)) return rc;
+    if (int rc = de.alloc(2)) return rc;
     HIP_TRY(hipMemset(dv, 0, 2 * sizeof(unsigned long long)));
     HIP_TRY(hipMemset(de, 0, 2 * sizeof(uint32_t)));
     HIP_TRY(gsr::launch_exp_probe(gsr_float_key(x_lo), gsr_float_key(x_hi), x_big, dv, de, nullptr));
@@ -2910,8 +2845,6 @@ extern "C" int gsr_exp_probe2(float x_lo, float x_hi, float x_big, int64_t* viol
     uint32_t e[2] = {0, 0};
     HIP_TRY(hipMemcpy(v, dv, sizeof v, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(e, de, sizeof e, hipMemcpyDeviceToHost));
-    (void)hipFree(dv);
-    (void)hipFree(de);
     *violations = (int64_t)v[0];
     *packed_mismatches = (int64_t)v[1];
     *err_all = gsr_bits_to_float(e[0]);
@@ -2929,14 +2862,12 @@ extern "C" int gsr_exp_probe(float x_lo, float x_hi, float x_big, int64_t* viola
 
 extern "C" int gsr_alpha_cut_probe(const float* host_op, int n, float* host_out) {
     if (!host_op || !host_out || n <= 0) return set_err(GSR_E_ARG, "gsr_alpha_cut_probe: bad argument");
-    float *din = nullptr, *dout = nullptr;
-    HIP_TRY(hipMalloc(&din, sizeof(float) * (size_t)n));
-    HIP_TRY(hipMalloc(&dout, sizeof(float) * (size_t)n));
+    DevBuf<float> din, dout;
+    if (int rc = din.alloc((size_t)n)) return rc;
+    if (int rc = dout.alloc((size_t)n)) return rc;
     HIP_TRY(hipMemcpy(din, host_op, sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
     HIP_TRY(gsr::launch_xs_probe(din, n, dout, nullptr));
     HIP_TRY(hipMemcpy(host_out, dout, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
-    (void)hipFree(din);
-    (void)hipFree(dout);
     return GSR_OK;
 }
 
@@ -3009,7 +2940,7 @@ extern "C" void preprocessCUDAGaussians(gsr_gaussian* d_gaussians, float* out_pi
     gsr_context* c = g_dropin;
     const size_t npx = 3 * (size_t)tile_W * (size_t)tile_H;
     if ((int64_t)npx > c->out_cap) {
-        if (realloc_dev(&c->out_tmp, npx)) { fail("alloc"); return; }
+        if (c->out_tmp.alloc(npx)) { fail("alloc"); return; }
         c->out_cap = (int64_t)npx;
     }
     const char* what = "render";
@@ -3036,22 +2967,16 @@ const char* gsr::last_error() { return g_err.c_str(); }
 namespace {
 
 struct SortBufs {
-    uint64_t* a = nullptr;
-    uint64_t* b = nullptr;
-    uint64_t* c = nullptr;
-    uint32_t* hist = nullptr;
-    uint32_t* totals = nullptr;
-    ~SortBufs() {
-        for (void* p : {(void*)a, (void*)b, (void*)c, (void*)hist, (void*)totals})
-            if (p) (void)hipFree(p);
-    }
+    DevBuf<uint64_t> a, b, c;
+    DevBuf<uint32_t> hist, totals;
     int alloc(uint32_t n, bool third) {
-        HIP_TRY(hipMalloc(&a, sizeof(uint64_t) * std::max<size_t>(n, 1)));
-        HIP_TRY(hipMalloc(&b, sizeof(uint64_t) * std::max<size_t>(n, 1)));
-        if (third) HIP_TRY(hipMalloc(&c, sizeof(uint64_t) * std::max<size_t>(n, 1)));
-        HIP_TRY(hipMalloc(&hist, sizeof(uint32_t) * 256 * gsr::kMaxSortGroups));
-        HIP_TRY(hipMalloc(&totals, sizeof(uint32_t) * 256));
-        return GSR_OK;
+        if (int rc = a.alloc(n)) return rc;
+        if (int rc = b.alloc(n)) return rc;
+        if (third) {
+            if (int rc = c.alloc(n)) return rc;
+        }
+        if (int rc = hist.alloc(256 * (size_t)gsr::kMaxSortGroups)) return rc;
+        return totals.alloc(256);
     }
 };
 
@@ -3082,8 +3007,8 @@ extern "C" void oneSweepSort(int* input, int* output, int N, int maxVal, float* 
     auto body = [&]() -> int {
         SortBufs sb;
         if (int rc = sb.alloc((uint32_t)N, false)) return rc;
-        int* dkeys = nullptr;
-        HIP_TRY(hipMalloc(&dkeys, sizeof(int) * (size_t)N));
+        DevBuf<int> dkeys;
+        if (int rc = dkeys.alloc((size_t)N)) return rc;
         HIP_TRY(hipMemcpy(dkeys, input, sizeof(int) * (size_t)N, hipMemcpyHostToDevice));
         hipEvent_t e0, e1;
         HIP_TRY(hipEventCreate(&e0));
@@ -3101,7 +3026,6 @@ extern "C" void oneSweepSort(int* input, int* output, int N, int maxVal, float* 
         HIP_TRY(hipMemcpy(output, dkeys, sizeof(int) * (size_t)N, hipMemcpyDeviceToHost));
         (void)hipEventDestroy(e0);
         (void)hipEventDestroy(e1);
-        (void)hipFree(dkeys);
         return GSR_OK;
     };
     if (body() != GSR_OK) std::fprintf(stderr, "oneSweepSort: %s\n", g_err.c_str());
@@ -3120,9 +3044,9 @@ extern "C" void oneSweep3DGaussianSort(gsr_lwg* d_in, int N, int num_bits, float
     auto body = [&]() -> int {
         SortBufs sb;
         if (int rc = sb.alloc((uint32_t)N, true)) return rc;
-        gsr_lwg *din = nullptr, *dout = nullptr;
-        HIP_TRY(hipMalloc(&din, sizeof(gsr_lwg) * (size_t)N));
-        HIP_TRY(hipMalloc(&dout, sizeof(gsr_lwg) * (size_t)N));
+        DevBuf<gsr_lwg> din, dout;
+        if (int rc = din.alloc((size_t)N)) return rc;
+        if (int rc = dout.alloc((size_t)N)) return rc;
         HIP_TRY(hipMemcpy(din, d_in, sizeof(gsr_lwg) * (size_t)N, hipMemcpyHostToDevice));
         hipEvent_t e0, e1;
         HIP_TRY(hipEventCreate(&e0));
@@ -3156,8 +3080,6 @@ extern "C" void oneSweep3DGaussianSort(gsr_lwg* d_in, int N, int num_bits, float
         HIP_TRY(hipMemcpy(d_in, dout, sizeof(gsr_lwg) * (size_t)N, hipMemcpyDeviceToHost));
         (void)hipEventDestroy(e0);
         (void)hipEventDestroy(e1);
-        (void)hipFree(din);
-        (void)hipFree(dout);
         return GSR_OK;
     };
     if (body() != GSR_OK) std::fprintf(stderr, "oneSweep3DGaussianSort: %s\n", g_err.c_str());
