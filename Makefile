@@ -15,13 +15,14 @@ LIB = gaussianrenderer_amd/lib/libgsr.so
 OBJDIR = build/obj
 SRCDIR = gaussianrenderer_amd/csrc
 HDRS = include/gsr.h include/gsr_types.h include/gsr_detmath.h $(SRCDIR)/gsr_internal.h
-DEVHDRS = $(SRCDIR)/gsr_device.h $(SRCDIR)/gsr_blend_device.h $(SRCDIR)/gsr_preprocess_device.h
+DEVHDRS = $(SRCDIR)/gsr_device.h $(SRCDIR)/gsr_blend_device.h $(SRCDIR)/gsr_preprocess_device.h \
+          $(SRCDIR)/gsr_geom_device.h
 
 all: $(LIB) oracle
 
 # the kernel translation units (gfx950 device code + launch wrappers); a stage that gets a
 # file of its own is added here
-KOBJS = $(addprefix $(OBJDIR)/,gsr_kernels.o gsr_blend.o gsr_blend_derived.o gsr_scene_ops.o gsr_scene_adam.o gsr_project.o gsr_probes.o)
+KOBJS = $(addprefix $(OBJDIR)/,gsr_kernels.o gsr_bucket_sort.o gsr_blend.o gsr_blend_derived.o gsr_scene_ops.o gsr_scene_adam.o gsr_project.o gsr_probes.o)
 
 $(OBJDIR)/%.o: $(SRCDIR)/%.hip $(HDRS) $(DEVHDRS)
 	mkdir -p $(OBJDIR)

@@ -1,6 +1,6 @@
 // gsr_internal.h — shared between the host runtime (gsr_runtime.cpp) and the
-// gfx950 kernels (gsr_kernels.hip, gsr_blend.hip, gsr_blend_derived.hip, gsr_scene_ops.hip,
-// gsr_scene_adam.hip, gsr_project.hip, gsr_probes.hip).  Not part of the public ABI.
+// gfx950 kernels (gsr_kernels.hip, gsr_bucket_sort.hip, gsr_blend.hip, gsr_blend_derived.hip,
+// gsr_scene_ops.hip, gsr_scene_adam.hip, gsr_project.hip, gsr_probes.hip).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -127,8 +127,9 @@ struct BlendSplit {
                                       // GSR_FRAME_SPEC_MISS into the frame's validity word (nullable)
 };
 
-// ---- launch wrappers (gsr_kernels.hip; the blend's in gsr_blend.hip, its derived passes' in
-// gsr_blend_derived.hip, the probes' in gsr_probes.hip) ----
+// ---- launch wrappers (gsr_kernels.hip; the bucket depth sort's in gsr_bucket_sort.hip, the
+// blend's in gsr_blend.hip, its derived passes' in gsr_blend_derived.hip, the probes' in
+// gsr_probes.hip) ----
 hipError_t launch_aos_to_soa(const gsr_gaussian* aos, int64_t n, float* arrays, int64_t stride,
                              hipStream_t s);
 hipError_t launch_preprocess(const float* arrays, int64_t stride, int64_t n, const Frame& fr,
@@ -163,7 +164,7 @@ hipError_t launch_radix_pass(const uint64_t* in, uint64_t* out, const uint32_t* 
                              uint32_t* pay1 = nullptr, bool rank_atomic = false,
                              const uint32_t* base_dev = nullptr, const uint32_t* gate = nullptr,
                              const SortFilter* filter = nullptr);
-// Bucket depth sort (binning path; gsr_kernels.hip "bucket depth sort"): the stable
+// Bucket depth sort (binning path; gsr_bucket_sort.hip "bucket depth sort"): the stable
 // (depth key, index) order of the n items `in` (the preprocess order; rect = its packed
 // tile rects by position) into items0 with the rects into pay0; items1 / pay1 are scratch.
 // buckets: 256..4096 (a power of two); s_in: its buckets - 1 sorted splitters (the last

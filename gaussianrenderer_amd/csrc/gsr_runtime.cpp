@@ -573,7 +573,7 @@ struct Settings {
     int rank_atomic = -1;            // GSR_TUNE_RANK_ATOMIC: 1 = ranks from returning LDS atomics when the
                                      // device self-check passed, 0 = ballot matching; -1 = not yet set
                                      // (the environment's GSR_RANK_ATOMIC=0 selects 0, else 1)
-    // bucket depth sort (GSR_TUNE_DEPTH_BUCKETS, gsr_kernels.hip "bucket depth sort")
+    // bucket depth sort (GSR_TUNE_DEPTH_BUCKETS, gsr_bucket_sort.hip "bucket depth sort")
     int fuse_rows = 1;               // GSR_TUNE_BUCKET_ROWS: the bucket sort's local kernel counts the row pass
     int col_chunk = 0;               // GSR_TUNE_COL_CHUNK: 0 = by scene size (col_chunk_for), 1024, 2048
     int bucket_sort = 1;             // 0 = LSD passes; 1 = bucket sort after the context's first frame
@@ -2392,7 +2392,7 @@ extern "C" int gsr_read_splats(gsr_context* c, void* host, int64_t n) {
     }
     HIP_TRY(hipMemcpy(host, c->rec, (size_t)n * GSR_SPLAT_RECORD_BYTES, hipMemcpyDeviceToHost));
     std::vector<uint64_t> rect((size_t)n), items((size_t)c->n);
-    if (c->rect_packed) {   // 4-B rects (gsr_kernels.hip pack_rect): tx0 | tx1 << 8 | ty0 << 16 | ty1 << 24
+    if (c->rect_packed) {   // 4-B rects (gsr_geom_device.h pack_rect): tx0 | tx1 << 8 | ty0 << 16 | ty1 << 24
         std::vector<uint32_t> p((size_t)n);
         HIP_TRY(hipMemcpy(p.data(), c->rect, (size_t)n * 4, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < (size_t)n; i++)

@@ -1,4 +1,4 @@
-"""The bucket depth sort (GSR_TUNE_DEPTH_BUCKETS, gsr_kernels.hip "bucket depth sort").
+"""The bucket depth sort (GSR_TUNE_DEPTH_BUCKETS, gsr_bucket_sort.hip "bucket depth sort").
 
 A context's first frame of a scene size runs the LSD passes and takes depth quantiles
 from their order; every later frame scatters the preprocess order stably into ~n/1024
@@ -454,7 +454,7 @@ def test_bucket_rows_fused_saturated_keys(gpu, orc, torch, tmp_path_factory):
 @pytest.mark.parametrize("hook", [1, 2])
 def test_big_buckets(gpu, orc, torch, tmp_path_factory, hook):
     """Knob 28 = 1 (default) above 2M Gaussians: 512 buckets of ~n / 512 items, each sorted by
-    one 1,024-thread workgroup in LDS (gsr_kernels.hip k_bbk_local), the scatter writing each
+    one 1,024-thread workgroup in LDS (gsr_bucket_sort.hip k_bbk_local), the scatter writing each
     tile in bucket order as 12-B records; 2 = the same with a 64-item capacity, so nearly every
     bucket goes to the second launch (k_bkt_local's paths).  2.3M Gaussians on a moving camera (stale splitters):
     the order equals the oracle's and the LSD passes', the tile lists and image too."""
