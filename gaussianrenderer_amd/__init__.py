@@ -25,6 +25,7 @@ from ._native import (AUX_MAX_FEATURES, AuxTargets, BackwardTargets, CONTRIB_WEI
                       LAYOUT_SCENE_BLOCK_SH3, NUM_STAGES, PLY_SH3, PLY_TYPED, SCENE4D_NARRAYS, SCENE_NARRAYS,
                       SCENE_SH3_NARRAYS, RecordGrads, SceneGrads,
                       ADAM_OPACITY_MAX, ADAM_OPACITY_MIN, ADAM_SKIP_ZERO, ADAM_ZERO_GRADS, AdamConfig,
+                      LOSS_NVALUES, LossConfig,
                       SPLAT_RECORD_BYTES, STAGES, TILE_PX, check, lib)
 
 __all__ = [
@@ -34,6 +35,7 @@ __all__ = [
     "CONTRIB_WEIGHT_ONE", "ContribTargets", "BackwardTargets", "mask_indices", "gather_planes",
     "RecordGrads", "SceneGrads",
     "AdamConfig", "ADAM_SKIP_ZERO", "ADAM_ZERO_GRADS", "ADAM_OPACITY_MIN", "ADAM_OPACITY_MAX", "SCENE_GRAD_GROUPS",
+    "LossConfig", "LOSS_NVALUES", "image_loss", "image_loss_scratch_bytes",
 ]
 
 # gsr_read_splats record (include/gsr.h).
@@ -302,6 +304,40 @@ def gather_planes(dst_ptr, dst_stride: int, src_ptr, src_stride: int, nplanes: i
     check(lib().gsr_gather_planes(dst, int(dst_stride), src, int(src_stride), int(nplanes), int(elem_bytes),
                                   int(n), idx, int(m), _dev_ptr(bad_ptr) or None, stream or None),
           "gsr_gather_planes")
+
+
+def image_loss_scratch_bytes(W: int, H: int, want_grad: bool = True) -> int:
+    """Bytes of device scratch gsr_image_loss needs for a W x H frame, with or without a
+    gradient (gsr_image_loss_scratch_bytes)."""
+    nbytes = lib().gsr_image_loss_scratch_bytes(int(W), int(H), 1 if want_grad else 0)
+    if nbytes < 0:
+        raise GsrError(int(nbytes), "gsr_image_loss_scratch_bytes")
+    return int(nbytes)
+
+
+def image_loss(image_ptr, target_ptr, W: int, H: int, *, w_l1: float = 0.8, w_l2: float = 0.0, w_dssim: float = 0.2,
+               grad_scale: float = 1.0, grad_ptr=None, loss_ptr=None, scratch_ptr, scratch_bytes: int | None = None,
+               stream: int = 0) -> None:
+    """The 3DGS training loss of a rendered frame against its target on the device, stream-
+    ordered (gsr_image_loss): w_l1 mean|x - y| + w_l2 mean (x - y)^2 + w_dssim (1 - mean SSIM).
+    grad_ptr (3*W*H floats, overwritten) receives grad_scale * dL/d image, the grad_image of
+    Renderer.render_backward_scene; loss_ptr (LOSS_NVALUES floats, overwritten) receives
+    {L, mean|x - y|, mean (x - y)^2, mean SSIM}.  At least one of the two.  scratch_ptr: device
+    memory of image_loss_scratch_bytes(W, H, grad_ptr is not None) bytes; scratch_bytes: what
+    it really holds (default: exactly that)."""
+    image, target, scratch = _dev_ptr(image_ptr), _dev_ptr(target_ptr), _dev_ptr(scratch_ptr)
+    grad, loss = _dev_ptr(grad_ptr), _dev_ptr(loss_ptr)
+    if not (image and target):
+        raise ValueError("image_loss: image_ptr / target_ptr is missing")
+    if not (grad or loss):
+        raise ValueError("image_loss: neither grad_ptr nor loss_ptr is given")
+    if not scratch:
+        raise ValueError("image_loss: scratch_ptr is missing")
+    if scratch_bytes is None:
+        scratch_bytes = image_loss_scratch_bytes(W, H, bool(grad))
+    cfg = LossConfig(float(w_l1), float(w_l2), float(w_dssim), float(grad_scale), 0)
+    check(lib().gsr_image_loss(image, target, int(W), int(H), byref(cfg), grad or None, loss or None, scratch,
+                               int(scratch_bytes), stream or None), "gsr_image_loss")
 
 
 def loadGaussianCudaFromPly(path: str):

@@ -172,6 +172,15 @@ class AdamConfig(ctypes.Structure):
     ]
 
 
+LOSS_NVALUES = 4   # GSR_LOSS_NVALUES: d_loss = {L, mean |x-y|, mean (x-y)^2, mean SSIM}
+
+
+class LossConfig(ctypes.Structure):
+    """``gsr_loss_config`` (include/gsr.h): the three weights, the gradient's scale, flags."""
+
+    _fields_ = [("w_l1", c_float), ("w_l2", c_float), ("w_dssim", c_float), ("grad_scale", c_float), ("flags", c_int)]
+
+
 # (name, restype, argtypes) for every symbol of include/gsr.h and include/gsr_gl.h.
 SIGNATURES = [
     ("preprocessCUDAGaussians", None,
@@ -257,6 +266,10 @@ SIGNATURES = [
     # scene optimisation (include/gsr.h)
     ("gsr_scene_adam_step", c_int, [c_void_p, c_int, c_int64, POINTER(SceneGrads), POINTER(SceneGrads),
                                     POINTER(SceneGrads), POINTER(AdamConfig), c_void_p, c_void_p]),
+    # image loss (include/gsr.h)
+    ("gsr_image_loss_scratch_bytes", c_int64, [c_int, c_int, c_int]),
+    ("gsr_image_loss", c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(LossConfig), c_void_p, c_void_p, c_void_p,
+                               c_int64, c_void_p]),
     ("gsr_ply_read_host", c_int, [c_char_p, c_void_p, c_int64, POINTER(c_int64)]),
     ("gsr_ply_read_host_ex", c_int, [c_char_p, c_void_p, c_int, c_int64, POINTER(c_int64), c_int, POINTER(c_int)]),
     ("gsr_synth_write_ply", c_int, [c_char_p, c_int64, c_uint64]),

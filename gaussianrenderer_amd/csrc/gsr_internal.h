@@ -1,6 +1,6 @@
 // gsr_internal.h — shared between the host runtime (gsr_runtime.cpp) and the
 // gfx950 kernels (gsr_kernels.hip, gsr_bucket_sort.hip, gsr_blend.hip, gsr_blend_derived.hip,
-// gsr_scene_ops.hip, gsr_scene_adam.hip, gsr_project.hip, gsr_probes.hip).  Not part of the public ABI.
+// gsr_scene_ops.hip, gsr_scene_adam.hip, gsr_image_loss.hip, gsr_project.hip, gsr_probes.hip).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -336,6 +336,22 @@ struct AdamLaunch {
 };
 hipError_t launch_scene_adam(float* arrays, int64_t stride, uint32_t n, const AdamLaunch& L, uint32_t* bad,
                              hipStream_t s);
+
+// Image loss (gsr_image_loss; gsr_image_loss.hip): a tiled forward launch, a one-workgroup sum
+// of the loss values (only with `loss`) and a tiled backward launch (only with `grad`).
+// scratch, in floats: kLossSlotFloats of per-workgroup {sum |d|, sum d^2, sum SSIM} (the tiled
+// launches run at most kLossMaxGroups workgroups, each walking tiles), then, only with `grad`,
+// the three partial maps of 3 * W * H each.  The host has checked every argument, the scratch
+// size among them (gsr_runtime.cpp); c_* are grad_scale * weight / (3 W H), signed and doubled
+// as the backward kernel adds them.
+constexpr int kLossMaxGroups = 2048;   // 8 workgroups of 256 threads for each of 256 CUs
+constexpr int64_t kLossSlotFloats = 3 * (int64_t)kLossMaxGroups;
+struct LossLaunch {
+    double w_l1, w_l2, w_dssim;
+    float c_l1, c_l2, c_ssim;
+};
+hipError_t launch_image_loss(const float* x, const float* y, int W, int H, const LossLaunch& L, float* grad,
+                             float* loss, float* scratch, hipStream_t s);
 
 // Device self-check of the lane order of same-address returning LDS atomics (the
 // RA rank path): runs k_rank_order_check synchronously on the current device and

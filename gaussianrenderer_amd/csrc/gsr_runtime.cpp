@@ -487,6 +487,52 @@ extern "C" int gsr_scene_adam_step(void* d_scene, int layout, int64_t n, const g
     return GSR_OK;
 }
 
+// ---- image loss (kernels: gsr_image_loss.hip) ----
+
+extern "C" int64_t gsr_image_loss_scratch_bytes(int W, int H, int want_grad) {
+    if (W < 1 || H < 1 || 3 * (int64_t)W * H > INT32_MAX)
+        return set_err(GSR_E_ARG, "gsr_image_loss_scratch_bytes: %d x %d out of range", W, H);
+    // the loss slots, then (with a gradient) three partial maps of 3 W H floats
+    return 4 * (gsr::kLossSlotFloats + (want_grad ? 9 * (int64_t)W * H : 0));
+}
+
+extern "C" int gsr_image_loss(const float* d_image, const float* d_target, int W, int H, const gsr_loss_config* cfg,
+                              float* d_grad_image, float* d_loss, void* d_scratch, int64_t scratch_bytes,
+                              void* stream) {
+    const char* who = "gsr_image_loss";
+    if (!d_image || !d_target || !cfg) return set_err(GSR_E_ARG, "%s: null image, target or cfg", who);
+    if (!d_grad_image && !d_loss) return set_err(GSR_E_ARG, "%s: neither a gradient nor the loss values asked for", who);
+    if (W < 1 || H < 1 || 3 * (int64_t)W * H > INT32_MAX) return set_err(GSR_E_ARG, "%s: %d x %d out of range", who, W, H);
+    const float ws[3] = {cfg->w_l1, cfg->w_l2, cfg->w_dssim};
+    for (float w : ws)
+        if (!std::isfinite(w) || w < 0.0f) return set_err(GSR_E_ARG, "%s: a weight is negative or not finite", who);
+    if (ws[0] == 0.0f && ws[1] == 0.0f && ws[2] == 0.0f) return set_err(GSR_E_ARG, "%s: every weight is 0", who);
+    if (!std::isfinite(cfg->grad_scale)) return set_err(GSR_E_ARG, "%s: grad_scale = %g", who, cfg->grad_scale);
+    if (cfg->flags) return set_err(GSR_E_ARG, "%s: unknown flag bits 0x%x", who, cfg->flags);
+    if (!d_scratch) return set_err(GSR_E_ARG, "%s: null scratch", who);
+    const int64_t need = gsr_image_loss_scratch_bytes(W, H, d_grad_image != nullptr);
+    if (scratch_bytes < need)
+        return set_err(GSR_E_ARG, "%s: scratch_bytes = %lld, %lld needed", who, (long long)scratch_bytes, (long long)need);
+    const uintptr_t align = reinterpret_cast<uintptr_t>(d_image) | reinterpret_cast<uintptr_t>(d_target) |
+                            reinterpret_cast<uintptr_t>(d_grad_image) | reinterpret_cast<uintptr_t>(d_loss) |
+                            reinterpret_cast<uintptr_t>(d_scratch);
+    if (align % 4) return set_err(GSR_E_ARG, "%s: misaligned pointer", who);
+    if (d_grad_image && (d_grad_image == d_image || d_grad_image == d_target))
+        return set_err(GSR_E_ARG, "%s: d_grad_image is d_image or d_target (the gradient launch reads both)", who);
+
+    const double per = (double)cfg->grad_scale / (3.0 * (double)W * (double)H);
+    gsr::LossLaunch L{};
+    L.w_l1 = (double)cfg->w_l1;
+    L.w_l2 = (double)cfg->w_l2;
+    L.w_dssim = (double)cfg->w_dssim;
+    L.c_l1 = (float)(L.w_l1 * per);
+    L.c_l2 = (float)(2.0 * L.w_l2 * per);
+    L.c_ssim = (float)(-L.w_dssim * per);
+    HIP_TRY(gsr::launch_image_loss(d_image, d_target, W, H, L, d_grad_image, d_loss, static_cast<float*>(d_scratch),
+                                   static_cast<hipStream_t>(stream)));
+    return GSR_OK;
+}
+
 extern "C" void* gsr_scene_upload(const float* host_soa, int64_t n) {
     return gsr_scene_upload_ex(host_soa, GSR_SCENE_NARRAYS, n);
 }

@@ -834,6 +834,69 @@ int gsr_scene_adam_step(void* d_scene, int layout, int64_t n,
                         const gsr_scene_grads* m, const gsr_scene_grads* v,   /* moments, same shapes, caller-owned */
                         const gsr_adam_config* cfg, uint32_t* d_bad, void* stream);
 
+/* ---- image loss: the step between gsr_render and gsr_render_backward_scene ----
+ *
+ * The LOSS of render -> LOSS -> gsr_render_backward_scene -> update: the 3DGS training loss
+ * of a rendered frame x = d_image against its target y = d_target, and dL/dx in the layout
+ * the backward reads.  x and y are 3*W*H floats, planar, in gsr_render's layout (the window
+ * below is symmetric, so the bottom-row-first order does not matter).  Context-free,
+ * stream-ordered: it never allocates or synchronises; what it needs between its launches
+ * lives in the caller's d_scratch.
+ *
+ *   L = w_l1 * mean|x - y| + w_l2 * mean (x - y)^2 + w_dssim * (1 - mean SSIM(x, y))
+ *
+ * with every mean over the 3*W*H elements (3DGS: w_l1 0.8, w_l2 0, w_dssim 0.2).  SSIM per
+ * channel and pixel, as 3DGS's ssim() computes it with conv2d(padding=5, groups=3):
+ *   g_k ~ exp(-(k - 5)^2 / (2 * 1.5^2)), k = 0..10, normalised to sum 1 in double and rounded
+ *   to float; the window is g x g, E[.] its weighted sum.  Pixels outside the image count as
+ *   0 in all five sums and the window is not renormalised at the border.
+ *   mu1 = E[x], mu2 = E[y], s1 = E[x^2] - mu1^2, s2 = E[y^2] - mu2^2, s12 = E[xy] - mu1 mu2
+ *   SSIM = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)),
+ *   C1 = 1e-4, C2 = 9e-4.
+ *
+ * d_loss (may be NULL) receives GSR_LOSS_NVALUES floats, OVERWRITTEN: {L, mean|x - y|,
+ * mean (x - y)^2 (the MSE: PSNR = -10 log10 of it), mean SSIM}.  They are not scaled by
+ * grad_scale.
+ * d_grad_image (may be NULL) receives grad_scale * dL/dx, 3*W*H floats, OVERWRITTEN, not
+ * accumulated (it is a per-frame input of the backward; grad_scale is 1 / batch size when
+ * several frames accumulate into one set of scene gradients).  The L1 term is sign(x - y)
+ * with sign(0) = 0; the D-SSIM term is the exact derivative through all five windowed sums (a
+ * second windowed sum, of three per-pixel partials).  d_target gets no gradient.  Images
+ * with x == y get the gradient 0 exactly.
+ *
+ * float32 throughout, written with explicit fused multiply-adds; the loss values are summed
+ * in double from per-workgroup partial sums, in a fixed order, by a last small launch.  No
+ * atomics and no completion counters: results are reproducible bit for bit for given inputs,
+ * and a value-only or a gradient-only call gives the bits of the combined call.  Non-finite
+ * inputs propagate (gsr_scene_adam_step skips and counts non-finite gradients).
+ *
+ * gsr_image_loss_scratch_bytes(W, H, want_grad) is what d_scratch must hold for a call with
+ * (want_grad != 0) or without a gradient; the value-only size is the smaller, and neither
+ * decreases when W*H grows.  The call never touches a byte at or past scratch_bytes; the
+ * contents of the scratch between calls are the implementation's and need no initialisation.
+ * Negative (GSR_E_ARG) when W or H < 1 or 3*W*H > INT32_MAX.
+ *
+ * GSR_E_ARG, before any device work: d_image, d_target or cfg NULL; both d_grad_image and
+ * d_loss NULL; W or H < 1 or 3*W*H > INT32_MAX; a weight negative or not finite; all three
+ * weights 0; grad_scale not finite; unknown flag bits; d_scratch NULL or scratch_bytes below
+ * the size of the mode asked for; a pointer that is not 4-byte aligned; d_grad_image equal to
+ * d_image or d_target (the gradient launch still reads both).  Any other overlap between the
+ * buffers is the caller's business and is not checked. */
+typedef struct gsr_loss_config {
+    float w_l1;        /* weight of mean |x - y|            (3DGS: 0.8) */
+    float w_l2;        /* weight of mean (x - y)^2          (3DGS: 0)   */
+    float w_dssim;     /* weight of 1 - mean SSIM(x, y)     (3DGS: 0.2) */
+    float grad_scale;  /* d_grad_image = grad_scale * dL/dx (1 / batch size; the loss values are not scaled) */
+    int   flags;       /* 0; unknown bits are refused */
+} gsr_loss_config;
+#define GSR_LOSS_NVALUES 4   /* d_loss: {L, mean |x-y|, mean (x-y)^2, mean SSIM} */
+
+int64_t gsr_image_loss_scratch_bytes(int W, int H, int want_grad);   /* >= 0, or a negative error code */
+int gsr_image_loss(const float* d_image, const float* d_target, int W, int H, const gsr_loss_config* cfg,
+                   float* d_grad_image /* 3*W*H, OVERWRITTEN, or NULL */,
+                   float* d_loss /* GSR_LOSS_NVALUES device floats, OVERWRITTEN, or NULL */,
+                   void* d_scratch, int64_t scratch_bytes, void* stream);
+
 /* ---------------------------------------------------------------- host helpers */
 
 /* PLY reader with the semantics of loadGaussianCudaFromPly (misc.cu:13-134 +
