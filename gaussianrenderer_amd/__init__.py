@@ -25,7 +25,7 @@ from ._native import (AUX_MAX_FEATURES, AuxTargets, BackwardTargets, CONTRIB_WEI
                       LAYOUT_SCENE_BLOCK_SH3, NUM_STAGES, PLY_SH3, PLY_TYPED, SCENE4D_NARRAYS, SCENE_NARRAYS,
                       SCENE_SH3_NARRAYS, RecordGrads, SceneGrads,
                       ADAM_OPACITY_MAX, ADAM_OPACITY_MIN, ADAM_SKIP_ZERO, ADAM_ZERO_GRADS, AdamConfig,
-                      LOSS_NVALUES, LossConfig,
+                      LOSS_NVALUES, LossConfig, DENSIFY_CHUNK,
                       SPLAT_RECORD_BYTES, STAGES, TILE_PX, check, lib)
 
 __all__ = [
@@ -36,6 +36,7 @@ __all__ = [
     "RecordGrads", "SceneGrads",
     "AdamConfig", "ADAM_SKIP_ZERO", "ADAM_ZERO_GRADS", "ADAM_OPACITY_MIN", "ADAM_OPACITY_MAX", "SCENE_GRAD_GROUPS",
     "LossConfig", "LOSS_NVALUES", "image_loss", "image_loss_scratch_bytes",
+    "densify_accumulate", "densify_gather_planes", "densify_normals", "DENSIFY_CHUNK",
 ]
 
 # gsr_read_splats record (include/gsr.h).
@@ -203,7 +204,7 @@ class Scene:
                   beta2: float = 0.999, eps: float = 1e-15, skip_zero: bool = False, zero_grads: bool = False,
                   bad_ptr=None, stream: int = 0) -> None:
         """One fused in-place Adam step of this block on the device (gsr_scene_adam_step,
-        include/gsr.h), stream-ordered: the one call that writes to a scene block.  grads (what
+        include/gsr.h), stream-ordered: with reset_opacity() the only call that writes to a scene block.  grads (what
         project_backward / render_backward_scene accumulated), m and v (the moments: same
         shapes, float32 planar [c*n + i], zeroed once by the caller) each name up to six device
         buffers: a dict with keys from SCENE_GRAD_GROUPS ("position" 3 planes, "opacity" 1,
@@ -233,6 +234,44 @@ class Scene:
                                  (ADAM_SKIP_ZERO if skip_zero else 0) | (ADAM_ZERO_GRADS if zero_grads else 0))
         check(lib().gsr_scene_adam_step(self.ptr or None, self.layout, self.n, byref(gs), byref(ms), byref(vs),
                                         byref(cfg), _dev_ptr(bad_ptr) or None, stream or None), "gsr_scene_adam_step")
+
+    def densify(self, grad_accum_ptr, seen_ptr, *, grad_threshold: float = 0.0002, scale_split: float,
+                min_opacity: float = 0.005, prune_scale_max: float = float("inf"), split_shrink: float = 1.6,
+                seed: int = 0, src_ptr=None, kind_ptr=None, stream: int = 0):
+        """3DGS's adaptive density control on the device (gsr_scene_densify, include/gsr.h):
+        returns (a new owned Scene, report dict).  grad_accum_ptr / seen_ptr: the statistic
+        densify_accumulate() summed (n floats / n uint32).  A Gaussian whose accum / seen
+        reaches grad_threshold is cloned when its largest scale is <= scale_split and split
+        into two children (scales / split_shrink, positions drawn from the parent under
+        `seed`) when it is larger; outputs whose opacity is below min_opacity or whose largest
+        scale exceeds prune_scale_max are dropped.  src_ptr (optional, room for 2n int32) and
+        kind_ptr (optional, room for 2n uint8) receive every output's source index and kind (0
+        the source itself, 1 its clone, 2 and 3 the children), for densify_gather_planes().
+        The report counts the sources: n_out, kept, cloned, split, pruned.  Synchronous on
+        `stream`."""
+        accum, seen = _dev_ptr(grad_accum_ptr), _dev_ptr(seen_ptr)
+        if self.n > 0 and not (accum and seen):
+            raise ValueError("Scene.densify: grad_accum_ptr / seen_ptr is missing")
+        cfg = _native.DensifyConfig(float(grad_threshold), float(scale_split), float(min_opacity),
+                                    float(prune_scale_max), float(split_shrink), int(seed) & (2 ** 64 - 1), 0)
+        rep = _native.DensifyReport()
+        ptr = lib().gsr_scene_densify(self.ptr or None, self.narrays, self.n, accum or None, seen or None, byref(cfg),
+                                      _dev_ptr(src_ptr) or None, _dev_ptr(kind_ptr) or None, byref(rep),
+                                      stream or None)
+        if not ptr:
+            raise GsrError(_native.GSR_E_ARG, "gsr_scene_densify")
+        report = {name: int(getattr(rep, name)) for name, _ in _native.DensifyReport._fields_}
+        return Scene(ptr, report["n_out"], narrays=self.narrays), report
+
+    def reset_opacity(self, cap: float = 0.01, m_opacity_ptr=None, v_opacity_ptr=None, stream: int = 0) -> None:
+        """3DGS's periodic opacity reset, in place and stream-ordered (gsr_scene_reset_opacity):
+        every stored opacity becomes min(opacity, cap) and the opacity group's two Adam moment
+        planes (optional, n floats each) are zeroed."""
+        if not self.ptr and self.n > 0:
+            raise ValueError("Scene.reset_opacity: the scene has been freed")
+        check(lib().gsr_scene_reset_opacity(self.ptr or None, self.layout, self.n, float(cap),
+                                            _dev_ptr(m_opacity_ptr) or None, _dev_ptr(v_opacity_ptr) or None,
+                                            stream or None), "gsr_scene_reset_opacity")
 
     def free(self):
         if self.ptr and self.owned:
@@ -304,6 +343,50 @@ def gather_planes(dst_ptr, dst_stride: int, src_ptr, src_stride: int, nplanes: i
     check(lib().gsr_gather_planes(dst, int(dst_stride), src, int(src_stride), int(nplanes), int(elem_bytes),
                                   int(n), idx, int(m), _dev_ptr(bad_ptr) or None, stream or None),
           "gsr_gather_planes")
+
+
+def densify_accumulate(center_ptr, n: int, W: int, H: int, grad_accum_ptr, seen_ptr, bad_ptr=None,
+                       stream: int = 0) -> None:
+    """The densification statistic of one backward frame, on the device and stream-ordered
+    (gsr_densify_accumulate): center_ptr names the two centre planes of render_backward
+    (center_ptr) or planes 8 and 9 of render_backward_scene's record scratch; every Gaussian a
+    pixel composited adds the norm of its centre gradient in NDC units to grad_accum_ptr (n
+    floats) and 1 to seen_ptr (n uint32).  Non-finite entries are skipped and counted into the
+    device uint32 bad_ptr (optional; zero it first)."""
+    center, accum, seen = _dev_ptr(center_ptr), _dev_ptr(grad_accum_ptr), _dev_ptr(seen_ptr)
+    if n > 0 and not (center and accum and seen):
+        raise ValueError("densify_accumulate: center_ptr / grad_accum_ptr / seen_ptr is missing")
+    check(lib().gsr_densify_accumulate(center or None, int(n), int(W), int(H), accum or None, seen or None,
+                                       _dev_ptr(bad_ptr) or None, stream or None), "gsr_densify_accumulate")
+
+
+def densify_gather_planes(dst_ptr, dst_stride: int, src_ptr, src_stride: int, nplanes: int, n: int, indices_ptr,
+                          kind_ptr, m: int, bad_ptr=None, stream: int = 0) -> None:
+    """dst[p*dst_stride + j] = 0 if kind[j] else src[p*src_stride + indices[j]] over float
+    planes, on the device, stream-ordered (gsr_densify_gather_planes): cuts the Adam moments
+    over to the scene Scene.densify() returned, through the lists it wrote — survivors keep
+    their moments, every new Gaussian starts at zero."""
+    dst, src, idx, kind = _dev_ptr(dst_ptr), _dev_ptr(src_ptr), _dev_ptr(indices_ptr), _dev_ptr(kind_ptr)
+    if not (idx and kind):
+        raise ValueError("densify_gather_planes: indices_ptr / kind_ptr is missing")
+    if not (dst and src):
+        raise ValueError("densify_gather_planes: dst_ptr / src_ptr is missing")
+    check(lib().gsr_densify_gather_planes(dst, int(dst_stride), src, int(src_stride), int(nplanes), int(n), idx, kind,
+                                          int(m), _dev_ptr(bad_ptr) or None, stream or None),
+          "gsr_densify_gather_planes")
+
+
+def densify_normals(seed: int, index, child) -> np.ndarray:
+    """The split sampler on the host (gsr_densify_normals): the three float32 normals of child
+    `child` of source `index` under `seed`, bit for bit what the split kernel draws; index and
+    child may be equal-length arrays (the result is then (len, 3))."""
+    idx, ch = np.atleast_1d(np.asarray(index, np.uint32)), np.atleast_1d(np.asarray(child, np.uint32))
+    idx, ch = np.broadcast_arrays(idx, ch)
+    out = np.zeros((idx.size, 3), np.float32)
+    f, base, s = lib().gsr_densify_normals, out.ctypes.data, int(seed) & (2 ** 64 - 1)
+    for j, (i, k) in enumerate(zip(idx.tolist(), ch.tolist())):
+        f(s, i, k, base + 12 * j)
+    return out if np.ndim(index) or np.ndim(child) else out[0]
 
 
 def image_loss_scratch_bytes(W: int, H: int, want_grad: bool = True) -> int:

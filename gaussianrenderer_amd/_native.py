@@ -172,6 +172,26 @@ class AdamConfig(ctypes.Structure):
     ]
 
 
+class DensifyConfig(ctypes.Structure):
+    """``gsr_densify_config`` (include/gsr.h): the thresholds of gsr_scene_densify, the split
+    children's shrink factor, the sampler's seed, flags."""
+
+    _fields_ = [
+        ("grad_threshold", c_float), ("scale_split", c_float), ("min_opacity", c_float),
+        ("prune_scale_max", c_float), ("split_shrink", c_float),
+        ("seed", c_uint64),
+        ("flags", c_int),
+    ]
+
+
+class DensifyReport(ctypes.Structure):
+    """``gsr_densify_report`` (include/gsr.h): the outputs and the sources by fate."""
+
+    _fields_ = [("n_out", c_int64), ("kept", c_int64), ("cloned", c_int64), ("split", c_int64), ("pruned", c_int64)]
+
+
+DENSIFY_CHUNK = 1024   # kDensifyChunk (gsr_internal.h): sources per workgroup of the expansion
+
 LOSS_NVALUES = 4   # GSR_LOSS_NVALUES: d_loss = {L, mean |x-y|, mean (x-y)^2, mean SSIM}
 
 
@@ -266,6 +286,15 @@ SIGNATURES = [
     # scene optimisation (include/gsr.h)
     ("gsr_scene_adam_step", c_int, [c_void_p, c_int, c_int64, POINTER(SceneGrads), POINTER(SceneGrads),
                                     POINTER(SceneGrads), POINTER(AdamConfig), c_void_p, c_void_p]),
+    # scene densification (include/gsr.h)
+    ("gsr_densify_accumulate", c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("gsr_scene_densify", c_void_p, [c_void_p, c_int, c_int64, c_void_p, c_void_p, POINTER(DensifyConfig), c_void_p,
+                                     c_void_p, POINTER(DensifyReport), c_void_p]),
+    ("gsr_densify_normals", None, [c_uint64, c_uint32, c_uint32, c_void_p]),
+    ("gsr_logf_probe", c_int, [c_void_p, c_int, c_void_p]),
+    ("gsr_densify_gather_planes", c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p,
+                                          c_int64, c_void_p, c_void_p]),
+    ("gsr_scene_reset_opacity", c_int, [c_void_p, c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
     # image loss (include/gsr.h)
     ("gsr_image_loss_scratch_bytes", c_int64, [c_int, c_int, c_int]),
     ("gsr_image_loss", c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(LossConfig), c_void_p, c_void_p, c_void_p,

@@ -1,6 +1,6 @@
 // gsr_internal.h — shared between the host runtime (gsr_runtime.cpp) and the
 // gfx950 kernels (gsr_kernels.hip, gsr_bucket_sort.hip, gsr_blend.hip, gsr_blend_derived.hip,
-// gsr_scene_ops.hip, gsr_scene_adam.hip, gsr_image_loss.hip, gsr_project.hip, gsr_probes.hip).  Not part of the public ABI.
+// gsr_scene_ops.hip, gsr_scene_densify.hip, gsr_scene_adam.hip, gsr_image_loss.hip, gsr_project.hip, gsr_probes.hip).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -12,6 +12,7 @@
 
 struct gsr_record_grads;   // include/gsr.h
 struct gsr_scene_grads;
+struct gsr_densify_config;
 
 namespace gsr {
 
@@ -313,6 +314,44 @@ hipError_t launch_mask_indices(const uint8_t* keep, uint32_t n, uint32_t* counts
 hipError_t launch_gather_planes(void* dst, int64_t dst_stride, const void* src, int64_t src_stride, int nplanes,
                                 int elem_bytes, uint32_t n, const int32_t* idx, uint32_t m, uint32_t* bad,
                                 void* scene_header, hipStream_t s);
+
+// The scan launch of launch_mask_indices on its own (k_mask_scan, one workgroup): counts[0 ..
+// chunks) become their exclusive prefix sums and counts[chunks] the total.  The densification's
+// expansion scans its chunk counts with it.
+hipError_t launch_scan_counts(uint32_t* counts, uint32_t chunks, hipStream_t s);
+
+// Scene densification (include/gsr.h "scene densification"; gsr_scene_densify.hip).  The host
+// has checked every argument (gsr_runtime.cpp); n == 0 (m == 0, n_out == 0) launches nothing.
+// launch_densify_accumulate: the statistic, one thread per Gaussian.
+// launch_densify_count: per chunk of kDensifyChunk sources its output count into counts
+// (densify_chunks(n) + 1 words, then scanned in place: the chunks' first output positions, and
+// n_out in the last word); totals: four zeroed words that receive the sources kept, cloned,
+// split and pruned (integer atomics, one per workgroup and fate).  launch_densify_emit: src[j]
+// / kind[j] of every output j < n_out from the scanned counts (the sources are classified
+// again: no per-source scratch).  launch_densify_split: the position and scale planes of
+// the outputs of kind 2 and 3 of the new block (dst, dst_stride), from their parents in the
+// source block; after the bulk move (launch_gather_planes on src).  launch_densify_gather:
+// dst[p][j] = kind[j] ? 0 : src[p][idx[j]], 4-byte elements, index rule of launch_gather_planes
+// for the indices it reads.  launch_reset_opacity: o = fminf(o, cap) over [0, n) of the
+// block's opacity array and zeros over [0, n) of the two moment planes (nullable).
+constexpr int kDensifyChunk = 1024;   // sources per workgroup of the expansion's kernels
+uint32_t densify_chunks(uint32_t n);
+hipError_t launch_densify_accumulate(const float* center, uint32_t n, int W, int H, float* accum, uint32_t* seen,
+                                     uint32_t* bad, hipStream_t s);
+hipError_t launch_densify_count(const float* arrays, int64_t stride, uint32_t n, const float* accum,
+                                const uint32_t* seen, const gsr_densify_config& cfg, uint32_t* counts,
+                                uint32_t* totals, hipStream_t s);
+hipError_t launch_densify_emit(const float* arrays, int64_t stride, uint32_t n, const float* accum,
+                               const uint32_t* seen, const gsr_densify_config& cfg, const uint32_t* offs,
+                               uint32_t n_out, int32_t* src, uint8_t* kind, hipStream_t s);
+hipError_t launch_densify_split(float* dst, int64_t dst_stride, uint32_t n_out, const float* arrays, int64_t stride,
+                                uint32_t n, const int32_t* src, const uint8_t* kind, float shrink, uint64_t seed,
+                                hipStream_t s);
+hipError_t launch_densify_gather(float* dst, int64_t dst_stride, const float* src, int64_t src_stride, int nplanes,
+                                 uint32_t n, const int32_t* idx, const uint8_t* kind, uint32_t m, uint32_t* bad,
+                                 hipStream_t s);
+hipError_t launch_reset_opacity(float* arrays, int64_t stride, uint32_t n, float cap, float* m_op, float* v_op,
+                                hipStream_t s);
 
 // Scene optimisation (gsr_scene_adam_step; k_scene_adam, gsr_scene_adam.hip): one launch steps
 // every active plane.  The plane table travels in the kernel arguments (the call never

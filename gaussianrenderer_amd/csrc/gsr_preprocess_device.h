@@ -2,7 +2,9 @@
 // record that its backward pass restates decisions of: the scene-array access, the loads, the
 // world-space covariance, the small matrix products and the cull tests.  Shared by
 // gsr_kernels.hip (k_preprocess, k_preprocess_multi) and gsr_project.hip (k_project_backward),
-// so that both take every decision on the same float32 values.
+// so that both take every decision on the same float32 values.  gsr_scene_densify.hip
+// (k_densify_split) takes the quaternion's rotation from here, so a split child moves along
+// the axes the preprocess draws.
 //
 // Every float expression restates render.cu / math.cu in the same operation order (the
 // translation units are compiled with -ffp-contract=off), and the transcendental functions
@@ -111,20 +113,26 @@ __device__ __forceinline__ void preprocess_load(const SoaWg& A, float tnow, PreL
     }
 }
 
-// World-space covariance R S S R^T of one Gaussian (render.cu:655-686, the part before
-// the camera rotation).
-__device__ __forceinline__ void preprocess_cov3d(const float* q_in, const float* s_in, float* cov) {
-    // buildRotMatFromQuat_cuda (math.cu:153-164)
+// Rotation matrix (row-major) of the normalised quaternion q_in = (w, x, y, z):
+// buildRotMatFromQuat_cuda (math.cu:153-164).  Shared with the densification's split kernel
+// (gsr_scene_densify.hip), which offsets a child along the same axes the preprocess draws.
+__device__ __forceinline__ void quat_rotation(const float* q_in, float* Rm) {
     float qw = q_in[0];
     float qx = q_in[1];
     float qy = q_in[2];
     float qz = q_in[3];
     const float qn = sqrtf(qx * qx + qy * qy + qz * qz + qw * qw);
     qx /= qn; qy /= qn; qz /= qn; qw /= qn;
-    float Rm[9], RT[9], S[9], tmp[9];
     Rm[0] = 1 - 2 * qy * qy - 2 * qz * qz; Rm[1] = 2 * qx * qy - 2 * qw * qz;     Rm[2] = 2 * qx * qz + 2 * qw * qy;
     Rm[3] = 2 * qx * qy + 2 * qw * qz;     Rm[4] = 1 - 2 * qx * qx - 2 * qz * qz; Rm[5] = 2 * qy * qz - 2 * qw * qx;
     Rm[6] = 2 * qx * qz - 2 * qw * qy;     Rm[7] = 2 * qy * qz + 2 * qw * qx;     Rm[8] = 1 - 2 * qx * qx - 2 * qy * qy;
+}
+
+// World-space covariance R S S R^T of one Gaussian (render.cu:655-686, the part before
+// the camera rotation).
+__device__ __forceinline__ void preprocess_cov3d(const float* q_in, const float* s_in, float* cov) {
+    float Rm[9], RT[9], S[9], tmp[9];
+    quat_rotation(q_in, Rm);
     RT[0] = Rm[0]; RT[1] = Rm[3]; RT[2] = Rm[6];
     RT[3] = Rm[1]; RT[4] = Rm[4]; RT[5] = Rm[7];
     RT[6] = Rm[2]; RT[7] = Rm[5]; RT[8] = Rm[8];

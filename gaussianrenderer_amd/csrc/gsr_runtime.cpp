@@ -487,6 +487,174 @@ extern "C" int gsr_scene_adam_step(void* d_scene, int layout, int64_t n, const g
     return GSR_OK;
 }
 
+// ---- scene densification (kernels: gsr_scene_densify.hip) ----
+
+extern "C" int gsr_densify_accumulate(const float* d_center, int64_t n, int W, int H, float* d_grad_accum,
+                                      uint32_t* d_seen, uint32_t* d_bad, void* stream) {
+    const char* who = "gsr_densify_accumulate";
+    if (n < 0 || n > INT32_MAX) return set_err(GSR_E_ARG, "%s: n = %lld out of range", who, (long long)n);
+    if (W < 1 || H < 1) return set_err(GSR_E_ARG, "%s: %d x %d out of range", who, W, H);
+    if (n > 0 && (!d_center || !d_grad_accum || !d_seen)) return set_err(GSR_E_ARG, "%s: null pointer", who);
+    const uintptr_t align = reinterpret_cast<uintptr_t>(d_center) | reinterpret_cast<uintptr_t>(d_grad_accum) |
+                            reinterpret_cast<uintptr_t>(d_seen) | reinterpret_cast<uintptr_t>(d_bad);
+    if (align % 4) return set_err(GSR_E_ARG, "%s: misaligned pointer", who);
+    if (n == 0) return GSR_OK;
+    HIP_TRY(gsr::launch_densify_accumulate(d_center, (uint32_t)n, W, H, d_grad_accum, d_seen, d_bad,
+                                           static_cast<hipStream_t>(stream)));
+    return GSR_OK;
+}
+
+// The argument errors of gsr_scene_densify's configuration (GSR_OK or GSR_E_ARG with the message set).
+static int check_densify_config(const gsr_densify_config& c, const char* who) {
+    const float f[5] = {c.grad_threshold, c.scale_split, c.min_opacity, c.prune_scale_max, c.split_shrink};
+    for (float x : f)
+        if (std::isnan(x)) return set_err(GSR_E_ARG, "%s: a NaN field in the configuration", who);
+    if (c.grad_threshold < 0.0f || c.scale_split < 0.0f)
+        return set_err(GSR_E_ARG, "%s: grad_threshold = %g or scale_split = %g negative", who, c.grad_threshold,
+                       c.scale_split);
+    if (c.min_opacity < 0.0f || c.min_opacity > 1.0f)
+        return set_err(GSR_E_ARG, "%s: min_opacity = %g outside [0, 1]", who, c.min_opacity);
+    if (!(c.prune_scale_max > 0.0f)) return set_err(GSR_E_ARG, "%s: prune_scale_max = %g <= 0", who, c.prune_scale_max);
+    if (!std::isfinite(c.split_shrink) || !(c.split_shrink > 1.0f))
+        return set_err(GSR_E_ARG, "%s: split_shrink = %g not finite or <= 1", who, c.split_shrink);
+    if (c.flags) return set_err(GSR_E_ARG, "%s: unknown flag bits 0x%x", who, c.flags);
+    return GSR_OK;
+}
+
+extern "C" void* gsr_scene_densify(const void* d_scene, int narrays, int64_t n, const float* d_grad_accum,
+                                   const uint32_t* d_seen, const gsr_densify_config* cfg, int32_t* d_src,
+                                   uint8_t* d_kind, gsr_densify_report* report, void* stream) {
+    const char* who = "gsr_scene_densify";
+    if (gsr_scene_bytes(narrays, n) < 0) return nullptr;   // bad narrays or n: the message is set
+    if (n > INT32_MAX / 2) {
+        set_err(GSR_E_ARG, "%s: n = %lld > INT32_MAX / 2 (the expansion can double it)", who, (long long)n);
+        return nullptr;
+    }
+    if (!d_scene || !cfg || !report || (n > 0 && (!d_grad_accum || !d_seen))) {
+        set_err(GSR_E_ARG, "%s: null pointer", who);
+        return nullptr;
+    }
+    if (check_densify_config(*cfg, who) != GSR_OK) return nullptr;
+    if ((reinterpret_cast<uintptr_t>(d_grad_accum) | reinterpret_cast<uintptr_t>(d_seen) |
+         reinterpret_cast<uintptr_t>(d_src)) % 4) {
+        set_err(GSR_E_ARG, "%s: misaligned pointer", who);
+        return nullptr;
+    }
+    if (check_scene_block(d_scene, narrays, n, who) != GSR_OK) return nullptr;
+
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const float* arrays = reinterpret_cast<const float*>(static_cast<const char*>(d_scene) + GSR_SCENE_HEADER_BYTES);
+    gsr_densify_report rep{};
+    DevBuf<uint32_t> counts;   // the chunk counts, their total (n_out), then the four fate totals
+    DevBuf<int32_t> own_src;
+    DevBuf<uint8_t> own_kind;
+    hipError_t e = hipSuccess;
+    const uint32_t chunks = n > 0 ? gsr::densify_chunks((uint32_t)n) : 0;
+    if (n > 0) {
+        if (counts.alloc((size_t)chunks + 5)) return nullptr;
+        uint32_t h[5] = {0, 0, 0, 0, 0};
+        e = hipMemsetAsync(counts + chunks + 1, 0, 4 * sizeof(uint32_t), s);
+        if (e == hipSuccess)
+            e = gsr::launch_densify_count(arrays, scene_stride(n), (uint32_t)n, d_grad_accum, d_seen, *cfg, counts,
+                                          counts + chunks + 1, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(h, counts + chunks, sizeof h, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            set_err(GSR_E_HIP, "%s: classification failed: %s", who, hipGetErrorString(e));
+            return nullptr;
+        }
+        rep.n_out = h[0];
+        rep.kept = h[1];
+        rep.cloned = h[2];
+        rep.split = h[3];
+        rep.pruned = h[4];
+        if (rep.kept + rep.cloned + rep.split + rep.pruned != n || rep.n_out != rep.kept + 2 * (rep.cloned + rep.split)) {
+            set_err(GSR_E_HIP, "%s: inconsistent expansion counts", who);
+            return nullptr;
+        }
+    }
+    const int64_t m = rep.n_out;
+    if (m > 0 && ((!d_src && own_src.alloc((size_t)m)) || (!d_kind && own_kind.alloc((size_t)m)))) return nullptr;
+    int32_t* src = d_src ? d_src : own_src.get();
+    uint8_t* kind = d_kind ? d_kind : own_kind.get();
+
+    const int64_t bytes = gsr_scene_bytes(narrays, m);
+    void* d = nullptr;
+    e = hipMalloc(&d, (size_t)bytes);
+    if (e != hipSuccess) {
+        set_err(GSR_E_HIP, "hipMalloc(%lld) failed: %s", (long long)bytes, hipGetErrorString(e));
+        return nullptr;
+    }
+    float* dst = reinterpret_cast<float*>(static_cast<char*>(d) + GSR_SCENE_HEADER_BYTES);
+    if (m > 0)
+        e = gsr::launch_densify_emit(arrays, scene_stride(n), (uint32_t)n, d_grad_accum, d_seen, *cfg, counts,
+                                     (uint32_t)m, src, kind, s);
+    // the bulk move (and the header, also for m == 0)
+    if (e == hipSuccess)
+        e = gsr::launch_gather_planes(dst, scene_stride(m), arrays, scene_stride(n), narrays, (int)sizeof(float),
+                                      (uint32_t)n, src, (uint32_t)m, nullptr, d, s);
+    if (e == hipSuccess && rep.split > 0)
+        e = gsr::launch_densify_split(dst, scene_stride(m), (uint32_t)m, arrays, scene_stride(n), (uint32_t)n, src, kind,
+                                      cfg->split_shrink, cfg->seed, s);
+    // the scratch and the private lists must outlive the launches that read them
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        set_err(GSR_E_HIP, "%s: expansion failed: %s", who, hipGetErrorString(e));
+        (void)hipFree(d);
+        return nullptr;
+    }
+    *report = rep;
+    return d;
+}
+
+extern "C" void gsr_densify_normals(uint64_t seed, uint32_t index, uint32_t child, float out3[3]) {
+    gsr_densify_normal3(seed, index, child, out3);
+}
+
+extern "C" int gsr_logf_probe(const float* host_in, int n, float* host_out) {
+    if (!host_in || !host_out || n < 0) return set_err(GSR_E_ARG, "gsr_logf_probe: bad argument");
+    for (int i = 0; i < n; i++) host_out[i] = gsr_logf(host_in[i]);
+    return GSR_OK;
+}
+
+extern "C" int gsr_densify_gather_planes(float* d_dst, int64_t dst_stride, const float* d_src_planes,
+                                         int64_t src_stride, int nplanes, int64_t n, const int32_t* d_src,
+                                         const uint8_t* d_kind, int64_t m, uint32_t* d_bad, void* stream) {
+    const char* who = "gsr_densify_gather_planes";
+    if (!d_dst || !d_src_planes || !d_src || !d_kind) return set_err(GSR_E_ARG, "%s: null pointer", who);
+    if (nplanes < 1) return set_err(GSR_E_ARG, "%s: nplanes = %d < 1", who, nplanes);
+    if (n < 0 || n > INT32_MAX || m < 0 || m > INT32_MAX || (m > 0 && n == 0))
+        return set_err(GSR_E_ARG, "%s: n = %lld, m = %lld out of range", who, (long long)n, (long long)m);
+    if (src_stride < n || dst_stride < m)
+        return set_err(GSR_E_ARG, "%s: stride smaller than its count (src %lld < %lld or dst %lld < %lld)", who,
+                       (long long)src_stride, (long long)n, (long long)dst_stride, (long long)m);
+    if ((reinterpret_cast<uintptr_t>(d_dst) | reinterpret_cast<uintptr_t>(d_src_planes) |
+         reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_bad)) % 4)
+        return set_err(GSR_E_ARG, "%s: misaligned pointer", who);
+    HIP_TRY(gsr::launch_densify_gather(d_dst, dst_stride, d_src_planes, src_stride, nplanes, (uint32_t)n, d_src, d_kind,
+                                       (uint32_t)m, d_bad, static_cast<hipStream_t>(stream)));
+    return GSR_OK;
+}
+
+extern "C" int gsr_scene_reset_opacity(void* d_scene, int layout, int64_t n, float cap, float* d_m_opacity,
+                                       float* d_v_opacity, void* stream) {
+    const char* who = "gsr_scene_reset_opacity";
+    if (layout != GSR_LAYOUT_SCENE_BLOCK && layout != GSR_LAYOUT_SCENE_BLOCK_4D && layout != GSR_LAYOUT_SCENE_BLOCK_SH3)
+        return set_err(GSR_E_ARG, "%s: layout %d is not a scene block", who, layout);
+    if (n < 0 || n > INT32_MAX) return set_err(GSR_E_ARG, "%s: n = %lld out of range", who, (long long)n);
+    if (n > 0 && !d_scene) return set_err(GSR_E_ARG, "%s: null scene", who);
+    if (!(cap >= GSR_ADAM_OPACITY_MIN && cap <= GSR_ADAM_OPACITY_MAX))
+        return set_err(GSR_E_ARG, "%s: cap = %g outside [%g, %g]", who, cap, GSR_ADAM_OPACITY_MIN, GSR_ADAM_OPACITY_MAX);
+    if ((reinterpret_cast<uintptr_t>(d_scene) | reinterpret_cast<uintptr_t>(d_m_opacity) |
+         reinterpret_cast<uintptr_t>(d_v_opacity)) % 4)
+        return set_err(GSR_E_ARG, "%s: misaligned pointer", who);
+    if (n == 0) return GSR_OK;
+    float* arrays = reinterpret_cast<float*>(static_cast<char*>(d_scene) + GSR_SCENE_HEADER_BYTES);
+    HIP_TRY(gsr::launch_reset_opacity(arrays, scene_stride(n), (uint32_t)n, cap, d_m_opacity, d_v_opacity,
+                                      static_cast<hipStream_t>(stream)));
+    return GSR_OK;
+}
+
 // ---- image loss (kernels: gsr_image_loss.hip) ----
 
 extern "C" int64_t gsr_image_loss_scratch_bytes(int W, int H, int want_grad) {

@@ -1,4 +1,5 @@
-// gsr_scene_adam.hip — the one writer of a scene block (include/gsr.h "scene optimisation"):
+// gsr_scene_adam.hip — the writer of a scene block besides the densification's opacity reset
+// (include/gsr.h "scene optimisation"):
 // a fused in-place Adam step over the block's arrays, from gsr_project_backward's gradient
 // planes and the caller's moment planes.
 #include "gsr_device.h"

@@ -192,6 +192,11 @@ hipError_t launch_mask_indices(const uint8_t* keep, uint32_t n, uint32_t* counts
     return hipGetLastError();
 }
 
+hipError_t launch_scan_counts(uint32_t* counts, uint32_t chunks, hipStream_t s) {
+    hipLaunchKernelGGL(k_mask_scan, dim3(1), dim3(256), 0, s, counts, chunks);
+    return hipGetLastError();
+}
+
 hipError_t launch_gather_planes(void* dst, int64_t dst_stride, const void* src, int64_t src_stride, int nplanes,
                                 int elem_bytes, uint32_t n, const int32_t* idx, uint32_t m, uint32_t* bad,
                                 void* scene_header, hipStream_t s) {

@@ -708,7 +708,7 @@ int gsr_scene_download(const void* d_scene, float* host_soa, int64_t n);
 /* ---- scene editing: new scene blocks from a keep mask or an index list, on the device ----
  *
  * The consumer half of gsr_render_contrib: a selection never edits a scene block in place (the
- * one writer of a block is gsr_scene_adam_step, below); these calls build
+ * two writers of a block are gsr_scene_adam_step and gsr_scene_reset_opacity, below); these calls build
  * a new one (a pruned scene, a level-of-detail or visibility subset, a reordered scene)
  * without the download / numpy / upload round trip, and cut the caller's per-Gaussian side
  * arrays (gsr_render_aux's feature planes, gsr_render_contrib's accumulators) down in step.
@@ -759,7 +759,8 @@ void* gsr_scene_gather(const void* d_scene, int narrays, int64_t n, const int32_
 void* gsr_scene_select(const void* d_scene, int narrays, int64_t n, const uint8_t* d_keep, int64_t* m_out,
                        int32_t* d_indices, void* stream);
 
-/* ---- scene optimisation: the one call that writes to a scene block ----
+/* ---- scene optimisation: the call that steps a scene block in place ----
+ * (gsr_scene_reset_opacity, under "scene densification", is the only other writer of a block)
  *
  * The update of render -> loss -> gsr_render_backward_scene -> UPDATE -> prune: one fused,
  * in-place Adam step of the block's arrays from gsr_project_backward's gradient planes, so a
@@ -833,6 +834,121 @@ int gsr_scene_adam_step(void* d_scene, int layout, int64_t n,
                         const gsr_scene_grads* grads,   /* gsr_project_backward's outputs */
                         const gsr_scene_grads* m, const gsr_scene_grads* v,   /* moments, same shapes, caller-owned */
                         const gsr_adam_config* cfg, uint32_t* d_bad, void* stream);
+
+/* ---- scene densification: clone, split and prune on the device ----
+ *
+ * The GROW step of render -> loss -> gsr_render_backward_scene -> gsr_scene_adam_step ->
+ * densify / prune: 3DGS's adaptive density control.  Small Gaussians with a large screen-space
+ * position gradient are cloned, large ones are split in two, and transparent or oversized
+ * ones are dropped, without the download / numpy / upload round trip.  All calls are
+ * context-free.
+ *
+ * 1. The statistic.  gsr_densify_accumulate reads the two centre planes gsr_render_backward
+ * wrote (d_center; planes 8 and 9 of gsr_render_backward_scene's record scratch): gx =
+ * d_center[i], gy = d_center[n + i].  Per Gaussian:
+ *   - gx and gy both +-0: not touched (no pixel composited it: gsr_project_backward's rule);
+ *   - gx or gy not finite: not touched, and *d_bad (may be NULL; a device word the caller
+ *     zeroes) is incremented;
+ *   - otherwise, in float32 with one rounding per operation,
+ *       a = gx * (0.5f * W),  b = gy * (0.5f * H)
+ *       d_grad_accum[i] += sqrtf((a * a) + (b * b)),  d_seen[i] += 1
+ *     W/2 and H/2 turn the pixel gradient into the NDC units of 3DGS's threshold 0.0002.
+ * Both arrays (n words each) ACCUMULATE and are never cleared by the library: the caller
+ * zeroes them once and again after every densify.  One thread owns one Gaussian, no atomics
+ * but *d_bad: reproducible bit for bit.  Stream-ordered, never allocates.
+ * GSR_E_ARG, before any device work: a NULL d_center, d_grad_accum or d_seen with n > 0; n
+ * outside [0, INT32_MAX]; W or H < 1; a pointer that is not 4-byte aligned.  n == 0 is GSR_OK
+ * without device work. */
+int gsr_densify_accumulate(const float* d_center /* 2 planes of n floats */, int64_t n, int W, int H,
+                           float* d_grad_accum /* n, ACCUMULATED */, uint32_t* d_seen /* n, ACCUMULATED */,
+                           uint32_t* d_bad /* or NULL */, void* stream);
+
+/* 2. The densify call.  For source i, every comparison in float32 as written (NaNs compare
+ * false):
+ *   avg   = d_seen[i] ? d_grad_accum[i] / (float)d_seen[i] : 0
+ *   hot   = avg >= grad_threshold
+ *   smax  = fmaxf(fmaxf(scale0, scale1), scale2) of the stored scales
+ *   split = hot && smax > scale_split,   clone = hot && !split
+ * A kept source emits itself (kind 0); a cloned one itself (kind 0) and then a bit-identical
+ * copy (kind 1); a split one its two children (kinds 2 and 3) and not itself.  The prune
+ * tests are applied to an output's own values, as 3DGS prunes after it has densified:
+ *   sout   = split ? smax / split_shrink : smax
+ *   pruned = stored opacity < min_opacity || sout > prune_scale_max
+ * (a child keeps its parent's opacity), so all outputs of a source share one fate and a source
+ * emits 0, 1 or 2 Gaussians.  Outputs appear in source index order, one source's outputs
+ * adjacent: one exclusive scan places them, and children stay beside their parent's neighbours
+ * in the preprocess order (the depth sort's tie-break).
+ *
+ * A split child (k = 0 for kind 2, k = 1 for kind 3) copies every array of its parent — SH,
+ * rotation, opacity, the temporal arrays of a 4D block — except the scales and the position:
+ *   s'_c = s_c / split_shrink
+ *   t_c  = z_c * s_c                     (s the PARENT's scales)
+ *   p'_r = p_r + ((R[r][0] * t0 + R[r][1] * t1) + R[r][2] * t2)
+ * R the rotation matrix of the normalised quaternion, by the preprocess's own expressions
+ * (math.cu:153-164), and (z0, z1, z2) = gsr_densify_normals(seed, i, k): the child's sample
+ * depends on (seed, i, k) alone, not on the other Gaussians' fates, the output position or the
+ * launch shape.  Non-finite values propagate without a special case.
+ *
+ * The result is a new scene block as gsr_scene_gather builds it (one hipMalloc; count n_out,
+ * stride rounded up to 64, the same narrays; free with gsr_scene_free); n_out == 0 gives a
+ * header-only block.  d_src[j] (may be NULL; room for 2n words) receives output j's source and
+ * d_kind[j] (may be NULL; room for 2n bytes) its kind; entries at n_out and beyond are left
+ * untouched.  *report (host) counts the SOURCES by fate — kept + cloned + split + pruned = n,
+ * n_out = kept + 2 (cloned + split) — and is written only on success.
+ * SYNCHRONOUS on `stream`, like gsr_scene_select (n_out must be known before the block is
+ * allocated); allocates and frees its own scratch (n / 256 bytes, and the lists the caller
+ * did not pass).  Everything is integer or one-owner arithmetic: reproducible bit for
+ * bit.  d_scene's header is checked against (narrays, n) as gsr_scene_select does.
+ * Returns NULL and sets gsr_last_error on failure.  GSR_E_ARG, before any device work: the
+ * cases gsr_scene_select refuses (a NULL d_scene, a bad narrays, n outside [0, INT32_MAX]); n >
+ * INT32_MAX / 2; a NULL cfg or report, or with n > 0 a NULL d_grad_accum or d_seen; a NaN
+ * field in cfg; grad_threshold or scale_split negative; min_opacity outside [0, 1];
+ * prune_scale_max <= 0; split_shrink not finite or <= 1; unknown flag bits. */
+typedef struct gsr_densify_config {
+    float grad_threshold;   /* hot when accum / seen >= this (3DGS 0.0002); +inf: nothing is hot */
+    float scale_split;      /* hot and max scale >  this: split;  hot and <= this: clone (3DGS: 0.01 * scene extent) */
+    float min_opacity;      /* outputs with stored opacity < this are dropped (3DGS 0.005); 0: off */
+    float prune_scale_max;  /* outputs with max scale > this are dropped (3DGS: 0.1 * extent); +inf: off */
+    float split_shrink;     /* a split child's scales are the parent's / this (3DGS 1.6 = 0.8 * 2) */
+    uint64_t seed;
+    int flags;              /* 0; unknown bits refused */
+} gsr_densify_config;
+typedef struct gsr_densify_report { int64_t n_out, kept, cloned, split, pruned; } gsr_densify_report; /* sources by fate */
+void* gsr_scene_densify(const void* d_scene, int narrays, int64_t n, const float* d_grad_accum, const uint32_t* d_seen,
+                        const gsr_densify_config* cfg, int32_t* d_src /* room for 2n, or NULL */,
+                        uint8_t* d_kind /* room for 2n, or NULL */, gsr_densify_report* report /* host */, void* stream);
+
+/* 3. The sampler, on the host: out3 = the three normals of child `child` of source `index`
+ * under `seed` — the host build of the code the split kernel runs (gsr_densify_normal3,
+ * gsr_detmath.h: Philox4x32-10 at counter (index, child, 0, 0) under key (seed low word, seed
+ * high word), then Box-Muller on gsr_logf, gsr_cosf and gsr_sinf), bit for bit what the device
+ * draws.  gsr_logf_probe: out[i] = gsr_logf(in[i]) for n host floats (positive normal values),
+ * for the accuracy sweep of the tests; GSR_E_ARG for a NULL pointer or n < 0. */
+void gsr_densify_normals(uint64_t seed, uint32_t index, uint32_t child, float out3[3]);
+int gsr_logf_probe(const float* host_in, int n, float* host_out);
+
+/* 4. Companions.
+ * gsr_densify_gather_planes cuts the Adam moments over to a densified scene in one call:
+ *   dst[p * dst_stride + j] = d_kind[j] ? +0 : src[p * src_stride + d_src[j]],  p < nplanes, j < m
+ * over float planes — survivors (kind 0) keep their moments and every new Gaussian starts at
+ * zero, as 3DGS does.  An index is read only where d_kind[j] == 0; there gsr_gather_planes'
+ * rule holds: no address is formed from an unchecked index, an index outside [0, n) reads
+ * element min(max(index, 0), n - 1) and *d_bad (may be NULL) counts it.  Stream-ordered, no
+ * allocation.  GSR_E_ARG as gsr_gather_planes (with elem_bytes 4), and for a NULL d_kind. */
+int gsr_densify_gather_planes(float* d_dst, int64_t dst_stride, const float* d_src_planes, int64_t src_stride,
+                              int nplanes, int64_t n, const int32_t* d_src, const uint8_t* d_kind, int64_t m,
+                              uint32_t* d_bad, void* stream);
+/* gsr_scene_reset_opacity: 3DGS's periodic opacity reset, the second call that writes to a
+ * scene block.  In place, o' = fminf(o, cap) for i < n (a NaN opacity becomes cap), and
+ * d_m_opacity[i] = d_v_opacity[i] = +0 for i < n (the opacity group's Adam moments; each may be
+ * NULL).  Elements [n, stride) and every other array keep their bits.  Stream-ordered, never
+ * allocates, synchronises or reads the block's header: it trusts (layout, n) as
+ * gsr_scene_adam_step does, and is ordered on `stream` under the same rules.
+ * GSR_E_ARG, before any device work: d_scene NULL with n > 0; GSR_LAYOUT_AOS or an unknown
+ * layout; n outside [0, INT32_MAX]; cap outside [GSR_ADAM_OPACITY_MIN, GSR_ADAM_OPACITY_MAX]
+ * (or NaN); a pointer that is not 4-byte aligned.  n == 0 is GSR_OK without device work. */
+int gsr_scene_reset_opacity(void* d_scene, int layout, int64_t n, float cap, float* d_m_opacity, float* d_v_opacity,
+                            void* stream);
 
 /* ---- image loss: the step between gsr_render and gsr_render_backward_scene ----
  *

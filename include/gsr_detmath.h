@@ -323,4 +323,88 @@ GSR_HD float gsr_atan2f(float y, float x) {
     return ysign ? -res : res;
 }
 
+/*
+ * logf(x) for positive NORMAL floats (the densification sampler's u in (0, 1]; zero,
+ * subnormal, negative and non-finite x are not handled).  Cephes logf: x = m 2^e with m in
+ * [sqrt(1/2), sqrt(2)) taken from the bits, r = m - 1 (exact), then
+ *   log m = r - r^2/2 + r^3 P(r),   log x = log m + e ln2 (ln2 in two parts),
+ * in plain float multiplies and adds only — no fma, no libm — so the host and the device
+ * round identically.  <= 2 ulp against double precision over every u = k 2^-24, k = 1 ..
+ * 2^24 (tests/test_densify_ref.py sweeps them all).
+ */
+GSR_HD float gsr_logf(float x) {
+    const uint32_t b = gsr_float_to_bits(x);
+    int e = (int)(b >> 23) - 126;
+    float m = gsr_bits_to_float((b & 0x007fffffu) | 0x3f000000u);   /* [0.5, 1) */
+    if (m < 0.707106781186547524f) {
+        e -= 1;
+        m = (m + m) - 1.0f;
+    } else {
+        m = m - 1.0f;
+    }
+    const float z = m * m;
+    float p = 7.0376836292e-2f;
+    p = (p * m) + -1.1514610310e-1f;
+    p = (p * m) + 1.1676998740e-1f;
+    p = (p * m) + -1.2420140846e-1f;
+    p = (p * m) + 1.4249322787e-1f;
+    p = (p * m) + -1.6668057665e-1f;
+    p = (p * m) + 2.0000714765e-1f;
+    p = (p * m) + -2.4999993993e-1f;
+    p = (p * m) + 3.3333331174e-1f;
+    const float fe = (float)e;
+    float y = m * (z * p);
+    y = y + (-2.12194440e-4f * fe);
+    y = y + (-0.5f * z);
+    return (m + y) + (0.693359375f * fe);
+}
+
+/*
+ * Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3",
+ * SC11; the Random123 generator): ten rounds of two 32 x 32 -> 64 multiplies on a 128-bit
+ * counter under a 64-bit key bumped by the Weyl constants between rounds.  The published
+ * known-answer vectors are pinned in tests/test_densify_ref.py.
+ */
+GSR_HD void gsr_philox4x32_10(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]) {
+    uint32_t c0 = counter[0], c1 = counter[1], c2 = counter[2], c3 = counter[3];
+    uint32_t k0 = key[0], k1 = key[1];
+    for (int r = 0; r < 10; r++) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1;
+        c3 = (uint32_t)p0;
+        c0 = n0;
+        c2 = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+/*
+ * The three standard normals of split child `child` of source Gaussian `index`
+ * (gsr_scene_densify, include/gsr.h): Philox under key = (seed low word, seed high word) at
+ * counter (index, child, 0, 0) gives x0..x3; with u(x) = ((x >> 8) + 1) 2^-24 in (0, 1] and
+ * v(x) = (x >> 8) 2^-24 in [0, 1), Box-Muller:
+ *   r1 = sqrtf(-2 gsr_logf(u(x0))), a1 = 6.2831855f v(x1): z0 = r1 gsr_cosf(a1), z1 = r1 gsr_sinf(a1)
+ *   z2 = sqrtf(-2 gsr_logf(u(x2))) gsr_cosf(6.2831855f v(x3))
+ * A sample depends on (seed, index, child) alone; |z| <= sqrt(48 ln 2) = 5.77.
+ */
+GSR_HD void gsr_densify_normal3(uint64_t seed, uint32_t index, uint32_t child, float z[3]) {
+    const uint32_t counter[4] = {index, child, 0u, 0u};
+    const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    uint32_t x[4];
+    gsr_philox4x32_10(counter, key, x);
+    const float s = 5.9604644775390625e-8f;   /* 2^-24 */
+    const float r1 = sqrtf(-2.0f * gsr_logf((float)((x[0] >> 8) + 1u) * s));
+    const float a1 = 6.2831855f * ((float)(x[1] >> 8) * s);
+    const float r2 = sqrtf(-2.0f * gsr_logf((float)((x[2] >> 8) + 1u) * s));
+    const float a2 = 6.2831855f * ((float)(x[3] >> 8) * s);
+    z[0] = r1 * gsr_cosf(a1);
+    z[1] = r1 * gsr_sinf(a1);
+    z[2] = r2 * gsr_cosf(a2);
+}
+
 #endif /* GSR_DETMATH_H */
