@@ -26,6 +26,7 @@ from ._native import (AUX_MAX_FEATURES, AuxTargets, BackwardTargets, CONTRIB_WEI
                       SCENE_SH3_NARRAYS, RecordGrads, SceneGrads,
                       ADAM_OPACITY_MAX, ADAM_OPACITY_MIN, ADAM_SKIP_ZERO, ADAM_ZERO_GRADS, AdamConfig,
                       LOSS_NVALUES, LossConfig, DENSIFY_CHUNK,
+                      InitConfig, KNN_BOUNDS_CHUNK, KNN_FAN, KNN_LEAF, KNN_SORT_TILE, SH_C0,
                       SPLAT_RECORD_BYTES, STAGES, TILE_PX, check, lib)
 
 __all__ = [
@@ -37,6 +38,8 @@ __all__ = [
     "AdamConfig", "ADAM_SKIP_ZERO", "ADAM_ZERO_GRADS", "ADAM_OPACITY_MIN", "ADAM_OPACITY_MAX", "SCENE_GRAD_GROUPS",
     "LossConfig", "LOSS_NVALUES", "image_loss", "image_loss_scratch_bytes",
     "densify_accumulate", "densify_gather_planes", "densify_normals", "DENSIFY_CHUNK",
+    "points_knn_scratch_bytes", "points_knn_dist2", "InitConfig", "KNN_LEAF", "KNN_FAN", "KNN_BOUNDS_CHUNK",
+    "KNN_SORT_TILE", "SH_C0",
 ]
 
 # gsr_read_splats record (include/gsr.h).
@@ -162,6 +165,46 @@ class Scene:
         if not ptr:
             raise GsrError(-3, f"loadGaussianCudaFromPly({path}): {lib().gsr_last_error().decode()}")
         return cls(ptr, n.value, narrays=na.value if (allow_4d or sh3) else SCENE_NARRAYS)
+
+    @classmethod
+    def from_points(cls, xyz_ptr, n: int, rgb_ptr=None, *, narrays: int = SCENE_NARRAYS, opacity: float = 0.1,
+                    min_dist2: float = 1e-7, scale_mul: float = 1.0, scale_max: float = float("inf"),
+                    t_center: float = 0.0, t_scale: float = 1.0, point_stride: int = 3, comp_stride: int = 1,
+                    rgb_point_stride: int = 3, rgb_comp_stride: int = 1, mean2_ptr=None, bad_ptr=None,
+                    stream: int = 0) -> "Scene":
+        """A new owned scene from a device point cloud, as 3DGS's create_from_pcd starts one
+        (gsr_scene_from_points, include/gsr.h): positions the points (n x 3 floats at xyz_ptr,
+        coordinate c of point i at i * point_stride + c * comp_stride), SH dc from the colours
+        in [0, 1] (rgb_ptr, the same addressing with its own strides; None: 0.5 grey), identity
+        rotation, one stored opacity, and every scale min(sqrt(max(mean2, min_dist2)) *
+        scale_mul, scale_max) with mean2 the exact mean squared distance to the point's three
+        nearest neighbours.  mean2_ptr (optional, n floats) receives mean2; bad_ptr (optional
+        device uint32; zero it first) counts the points with a non-finite coordinate, which
+        are copied as they are and are nobody's neighbour.  t_center / t_scale: the stored
+        temporal centre and scale of a 4D block.  Synchronous on `stream`."""
+        xyz, rgb = _dev_ptr(xyz_ptr), _dev_ptr(rgb_ptr)
+        if n > 0 and not xyz:
+            raise ValueError("Scene.from_points: xyz_ptr is missing")
+        if narrays not in (SCENE_NARRAYS, SCENE4D_NARRAYS, SCENE_SH3_NARRAYS):
+            raise ValueError(f"Scene.from_points: narrays = {narrays}")
+        cfg = InitConfig(float(opacity), float(min_dist2), float(scale_mul), float(scale_max), float(t_center),
+                         float(t_scale), 0)
+        ptr = lib().gsr_scene_from_points(xyz or None, int(point_stride), int(comp_stride), rgb or None,
+                                          int(rgb_point_stride), int(rgb_comp_stride), int(n), int(narrays),
+                                          byref(cfg), _dev_ptr(mean2_ptr) or None, _dev_ptr(bad_ptr) or None,
+                                          stream or None)
+        if not ptr:
+            raise GsrError(_native.GSR_E_ARG, "gsr_scene_from_points")
+        return cls(ptr, int(n), narrays=int(narrays))
+
+    def knn_dist2(self, out_ptr, scratch_ptr, scratch_bytes: int, bad_ptr=None, stream: int = 0) -> None:
+        """points_knn_dist2() on this block's own positions (its x, y, z arrays, planar with the
+        block's stride), stream-ordered: out_ptr receives n floats."""
+        if not self.ptr and self.n > 0:
+            raise ValueError("Scene.knn_dist2: the scene has been freed")
+        stride = (self.n + 63) // 64 * 64
+        points_knn_dist2(self.ptr + _native.SCENE_HEADER_BYTES if self.ptr else None, self.n, out_ptr, scratch_ptr,
+                         scratch_bytes, point_stride=1, comp_stride=max(stride, 2), bad_ptr=bad_ptr, stream=stream)
 
     def download(self) -> np.ndarray:
         soa = np.zeros((self.narrays, self.n), dtype=np.float32)
@@ -374,6 +417,33 @@ def densify_gather_planes(dst_ptr, dst_stride: int, src_ptr, src_stride: int, np
     check(lib().gsr_densify_gather_planes(dst, int(dst_stride), src, int(src_stride), int(nplanes), int(n), idx, kind,
                                           int(m), _dev_ptr(bad_ptr) or None, stream or None),
           "gsr_densify_gather_planes")
+
+
+def points_knn_scratch_bytes(n: int) -> int:
+    """Bytes of device scratch points_knn_dist2() needs for n points (about 32 n)."""
+    b = int(lib().gsr_points_knn_scratch_bytes(int(n)))
+    if b < 0:
+        raise GsrError(b, "gsr_points_knn_scratch_bytes")
+    return b
+
+
+def points_knn_dist2(xyz_ptr, n: int, out_ptr, scratch_ptr, scratch_bytes: int, *, point_stride: int = 3,
+                     comp_stride: int = 1, bad_ptr=None, stream: int = 0) -> None:
+    """out[i] = the mean squared distance from point i to its three nearest neighbours, exact
+    in float32 and reproducible bit for bit, on the device and stream-ordered
+    (gsr_points_knn_dist2, include/gsr.h): what 3DGS initialises its scales from.  Coordinate c
+    of point i is at xyz_ptr[i * point_stride + c * comp_stride] (floats): (3, 1) an interleaved
+    [n, 3] tensor, (1, S) planar.  Points with a non-finite coordinate are nobody's neighbour,
+    get 0 and count into the device uint32 bad_ptr (optional; zero it first).  scratch_ptr:
+    points_knn_scratch_bytes(n) bytes of device memory, the call's only working memory."""
+    xyz, out, scratch = _dev_ptr(xyz_ptr), _dev_ptr(out_ptr), _dev_ptr(scratch_ptr)
+    if n > 0 and not (xyz and out):
+        raise ValueError("points_knn_dist2: xyz_ptr / out_ptr is missing")
+    if n > 0 and not scratch:
+        raise ValueError("points_knn_dist2: scratch_ptr is missing")
+    check(lib().gsr_points_knn_dist2(xyz or None, int(point_stride), int(comp_stride), int(n), out or None,
+                                     _dev_ptr(bad_ptr) or None, scratch or None, max(int(scratch_bytes), 0),
+                                     stream or None), "gsr_points_knn_dist2")
 
 
 def densify_normals(seed: int, index, child) -> np.ndarray:

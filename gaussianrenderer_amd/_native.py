@@ -47,6 +47,7 @@ SPLAT_RECORD_BYTES = 64
 SCENE_NARRAYS = 38
 SCENE4D_NARRAYS = 49
 SCENE_SH3_NARRAYS = 59
+SCENE_HEADER_BYTES = 256
 
 
 class Camera(ctypes.Structure):
@@ -192,6 +193,25 @@ class DensifyReport(ctypes.Structure):
 
 DENSIFY_CHUNK = 1024   # kDensifyChunk (gsr_internal.h): sources per workgroup of the expansion
 
+
+class InitConfig(ctypes.Structure):
+    """``gsr_init_config`` (include/gsr.h): what gsr_scene_from_points fills a new block with."""
+
+    _fields_ = [
+        ("opacity", c_float), ("min_dist2", c_float), ("scale_mul", c_float), ("scale_max", c_float),
+        ("t_center", c_float), ("t_scale", c_float),
+        ("flags", c_int),
+    ]
+
+
+# the k-NN structure's constants (gsr_internal.h): points per leaf, boxes per coarser box,
+# points per workgroup of the bounds kernel, items per workgroup of a sort pass
+KNN_LEAF = 64
+KNN_FAN = 64
+KNN_BOUNDS_CHUNK = 2048
+KNN_SORT_TILE = 4096
+SH_C0 = 0.28209479177387814   # the preprocess's constant: colour = 0.5 + SH_C0 * dc
+
 LOSS_NVALUES = 4   # GSR_LOSS_NVALUES: d_loss = {L, mean |x-y|, mean (x-y)^2, mean SSIM}
 
 
@@ -295,6 +315,12 @@ SIGNATURES = [
     ("gsr_densify_gather_planes", c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p,
                                           c_int64, c_void_p, c_void_p]),
     ("gsr_scene_reset_opacity", c_int, [c_void_p, c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
+    # scene initialisation (include/gsr.h)
+    ("gsr_points_knn_scratch_bytes", c_int64, [c_int64]),
+    ("gsr_points_knn_dist2", c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                     ctypes.c_size_t, c_void_p]),
+    ("gsr_scene_from_points", c_void_p, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int,
+                                         POINTER(InitConfig), c_void_p, c_void_p, c_void_p]),
     # image loss (include/gsr.h)
     ("gsr_image_loss_scratch_bytes", c_int64, [c_int, c_int, c_int]),
     ("gsr_image_loss", c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(LossConfig), c_void_p, c_void_p, c_void_p,

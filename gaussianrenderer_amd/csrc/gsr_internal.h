@@ -1,6 +1,6 @@
 // gsr_internal.h — shared between the host runtime (gsr_runtime.cpp) and the
 // gfx950 kernels (gsr_kernels.hip, gsr_bucket_sort.hip, gsr_blend.hip, gsr_blend_derived.hip,
-// gsr_scene_ops.hip, gsr_scene_densify.hip, gsr_scene_adam.hip, gsr_image_loss.hip, gsr_project.hip, gsr_probes.hip).  Not part of the public ABI.
+// gsr_scene_ops.hip, gsr_scene_densify.hip, gsr_scene_init.hip, gsr_scene_adam.hip, gsr_image_loss.hip, gsr_project.hip, gsr_probes.hip).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -13,6 +13,7 @@
 struct gsr_record_grads;   // include/gsr.h
 struct gsr_scene_grads;
 struct gsr_densify_config;
+struct gsr_init_config;
 
 namespace gsr {
 
@@ -352,6 +353,27 @@ hipError_t launch_densify_gather(float* dst, int64_t dst_stride, const float* sr
                                  hipStream_t s);
 hipError_t launch_reset_opacity(float* arrays, int64_t stride, uint32_t n, float cap, float* m_op, float* v_op,
                                 hipStream_t s);
+
+// Scene initialisation (include/gsr.h "scene initialisation"; gsr_scene_init.hip).  The host has
+// checked every argument (gsr_runtime.cpp).  launch_points_knn: the exact 3-NN statistic of n
+// points into mean2, all working memory in `scratch` (knn_scratch_bytes(n) bytes: the bounds,
+// two item buffers and the histograms of the sort, the sorted position planes, three box
+// levels); n == 0 launches nothing.  The structure's constants, which the tests straddle: a
+// leaf is kKnnLeaf consecutive points of the sorted order (one wave), a box of a coarser level
+// covers kKnnFan boxes of the level below, the bounds kernel's workgroup takes kKnnBoundsChunk
+// points and a sort pass's kSortTile.  launch_scene_init_fill: the header and every array of the
+// new block (also for n == 0: the header alone) from the points, the colours (nullable) and
+// mean2.
+constexpr int kKnnLeaf = 64;
+constexpr int kKnnFan = 64;
+constexpr int kKnnBoundsChunk = 2048;
+int64_t knn_scratch_bytes(int64_t n);
+hipError_t launch_points_knn(const float* xyz, int64_t point_stride, int64_t comp_stride, uint32_t n, float* mean2,
+                             uint32_t* bad, void* scratch, hipStream_t s);
+hipError_t launch_scene_init_fill(void* block, int64_t stride, int narrays, const float* xyz, int64_t point_stride,
+                                  int64_t comp_stride, const float* rgb, int64_t rgb_point_stride,
+                                  int64_t rgb_comp_stride, uint32_t n, const float* mean2, const gsr_init_config& cfg,
+                                  hipStream_t s);
 
 // Scene optimisation (gsr_scene_adam_step; k_scene_adam, gsr_scene_adam.hip): one launch steps
 // every active plane.  The plane table travels in the kernel arguments (the call never

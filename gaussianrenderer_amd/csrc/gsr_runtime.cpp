@@ -655,6 +655,114 @@ extern "C" int gsr_scene_reset_opacity(void* d_scene, int layout, int64_t n, flo
     return GSR_OK;
 }
 
+// ---- scene initialisation (kernels: gsr_scene_init.hip) ----
+
+extern "C" int64_t gsr_points_knn_scratch_bytes(int64_t n) {
+    if (n < 0 || n > INT32_MAX) return set_err(GSR_E_ARG, "gsr_points_knn_scratch_bytes: n = %lld out of range", (long long)n);
+    return gsr::knn_scratch_bytes(n);
+}
+
+// The argument errors of a strided [n, 3] array (GSR_OK or GSR_E_ARG with the message set).
+static int check_point_strides(int64_t ps, int64_t cs, int64_t n, const char* who, const char* what) {
+    if (ps < 1 || cs < 1) return set_err(GSR_E_ARG, "%s: %s stride < 1 (%lld, %lld)", who, what, (long long)ps, (long long)cs);
+    // cs <= INT64_MAX / 3 and ps <= INT64_MAX / n keep the products exact; anything larger is
+    // no array a device holds
+    if (cs > INT64_MAX / 3 || (n > 0 && ps > INT64_MAX / n))
+        return set_err(GSR_E_ARG, "%s: %s strides (%lld, %lld) out of range", who, what, (long long)ps, (long long)cs);
+    if (ps == cs || !(ps >= 3 * cs || cs >= n * ps))
+        return set_err(GSR_E_ARG, "%s: %s strides (%lld, %lld) overlap for n = %lld", who, what, (long long)ps,
+                       (long long)cs, (long long)n);
+    return GSR_OK;
+}
+
+// gsr_points_knn_dist2's argument errors but the scratch's.
+static int check_knn_args(const float* d_xyz, int64_t ps, int64_t cs, int64_t n, const float* d_mean2,
+                          const uint32_t* d_bad, const char* who) {
+    if (n < 0 || n > INT32_MAX) return set_err(GSR_E_ARG, "%s: n = %lld out of range", who, (long long)n);
+    if (n > 0 && !d_xyz) return set_err(GSR_E_ARG, "%s: null d_xyz", who);
+    if (int rc = check_point_strides(ps, cs, n, who, "point")) return rc;
+    if ((reinterpret_cast<uintptr_t>(d_xyz) | reinterpret_cast<uintptr_t>(d_mean2) | reinterpret_cast<uintptr_t>(d_bad)) % 4)
+        return set_err(GSR_E_ARG, "%s: misaligned pointer", who);
+    return GSR_OK;
+}
+
+extern "C" int gsr_points_knn_dist2(const float* d_xyz, int64_t point_stride, int64_t comp_stride, int64_t n,
+                                    float* d_mean2, uint32_t* d_bad, void* d_scratch, size_t scratch_bytes,
+                                    void* stream) {
+    const char* who = "gsr_points_knn_dist2";
+    if (int rc = check_knn_args(d_xyz, point_stride, comp_stride, n, d_mean2, d_bad, who)) return rc;
+    if (n > 0 && (!d_mean2 || !d_scratch)) return set_err(GSR_E_ARG, "%s: null d_mean2 or d_scratch", who);
+    if (reinterpret_cast<uintptr_t>(d_scratch) % 4) return set_err(GSR_E_ARG, "%s: misaligned pointer", who);
+    const int64_t need = gsr::knn_scratch_bytes(n);
+    if ((uint64_t)scratch_bytes < (uint64_t)need)
+        return set_err(GSR_E_ARG, "%s: scratch_bytes = %zu, %lld needed", who, scratch_bytes, (long long)need);
+    if (n == 0) return GSR_OK;
+    HIP_TRY(gsr::launch_points_knn(d_xyz, point_stride, comp_stride, (uint32_t)n, d_mean2, d_bad, d_scratch,
+                                   static_cast<hipStream_t>(stream)));
+    return GSR_OK;
+}
+
+extern "C" void* gsr_scene_from_points(const float* d_xyz, int64_t point_stride, int64_t comp_stride, const float* d_rgb,
+                                       int64_t rgb_point_stride, int64_t rgb_comp_stride, int64_t n, int narrays,
+                                       const gsr_init_config* cfg, float* d_mean2, uint32_t* d_bad, void* stream) {
+    const char* who = "gsr_scene_from_points";
+    if (check_knn_args(d_xyz, point_stride, comp_stride, n, d_mean2, d_bad, who) != GSR_OK) return nullptr;
+    if (d_rgb && check_point_strides(rgb_point_stride, rgb_comp_stride, n, who, "rgb") != GSR_OK) return nullptr;
+    if (reinterpret_cast<uintptr_t>(d_rgb) % 4) {
+        set_err(GSR_E_ARG, "%s: misaligned pointer", who);
+        return nullptr;
+    }
+    if (narrays != GSR_SCENE_NARRAYS && narrays != GSR_SCENE4D_NARRAYS && narrays != GSR_SCENE_SH3_NARRAYS) {
+        set_err(GSR_E_ARG, "%s: narrays = %d", who, narrays);
+        return nullptr;
+    }
+    if (!cfg) {
+        set_err(GSR_E_ARG, "%s: null cfg", who);
+        return nullptr;
+    }
+    const float f[6] = {cfg->opacity, cfg->min_dist2, cfg->scale_mul, cfg->scale_max, cfg->t_center, cfg->t_scale};
+    int bad_cfg = 0;
+    for (float x : f)
+        if (std::isnan(x)) bad_cfg = set_err(GSR_E_ARG, "%s: a NaN field in the configuration", who);
+    if (!bad_cfg && !(cfg->opacity >= GSR_ADAM_OPACITY_MIN && cfg->opacity <= GSR_ADAM_OPACITY_MAX))
+        bad_cfg = set_err(GSR_E_ARG, "%s: opacity = %g outside [%g, %g]", who, cfg->opacity, GSR_ADAM_OPACITY_MIN,
+                          GSR_ADAM_OPACITY_MAX);
+    if (!bad_cfg && cfg->min_dist2 < 0.0f) bad_cfg = set_err(GSR_E_ARG, "%s: min_dist2 = %g < 0", who, cfg->min_dist2);
+    if (!bad_cfg && (!std::isfinite(cfg->scale_mul) || !(cfg->scale_mul > 0.0f)))
+        bad_cfg = set_err(GSR_E_ARG, "%s: scale_mul = %g not finite or <= 0", who, cfg->scale_mul);
+    if (!bad_cfg && !(cfg->scale_max > 0.0f)) bad_cfg = set_err(GSR_E_ARG, "%s: scale_max = %g <= 0", who, cfg->scale_max);
+    if (!bad_cfg && narrays == GSR_SCENE4D_NARRAYS && !(cfg->t_scale > 0.0f))
+        bad_cfg = set_err(GSR_E_ARG, "%s: t_scale = %g <= 0 on a 4D block", who, cfg->t_scale);
+    if (!bad_cfg && cfg->flags) bad_cfg = set_err(GSR_E_ARG, "%s: unknown flag bits 0x%x", who, cfg->flags);
+    if (bad_cfg) return nullptr;
+
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // the k-NN scratch, then the statistic when the caller did not ask for it
+    const size_t knn_bytes = (size_t)gsr::knn_scratch_bytes(n);
+    DevBuf<char> scratch;
+    if (n > 0 && scratch.alloc(knn_bytes + (d_mean2 ? 0 : sizeof(float) * (size_t)n))) return nullptr;
+    float* mean2 = d_mean2 ? d_mean2 : reinterpret_cast<float*>(scratch.get() + knn_bytes);
+    const int64_t bytes = gsr_scene_bytes(narrays, n);
+    void* d = nullptr;
+    hipError_t e = hipMalloc(&d, (size_t)bytes);
+    if (e != hipSuccess) {
+        set_err(GSR_E_HIP, "hipMalloc(%lld) failed: %s", (long long)bytes, hipGetErrorString(e));
+        return nullptr;
+    }
+    e = gsr::launch_points_knn(d_xyz, point_stride, comp_stride, (uint32_t)n, mean2, d_bad, scratch.get(), s);
+    if (e == hipSuccess)
+        e = gsr::launch_scene_init_fill(d, scene_stride(n), narrays, d_xyz, point_stride, comp_stride, d_rgb,
+                                        rgb_point_stride, rgb_comp_stride, (uint32_t)n, mean2, *cfg, s);
+    // the scratch must outlive the launches that use it
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        set_err(GSR_E_HIP, "%s failed: %s", who, hipGetErrorString(e));
+        (void)hipFree(d);
+        return nullptr;
+    }
+    return d;
+}
+
 // ---- image loss (kernels: gsr_image_loss.hip) ----
 
 extern "C" int64_t gsr_image_loss_scratch_bytes(int W, int H, int want_grad) {

@@ -950,6 +950,94 @@ int gsr_densify_gather_planes(float* d_dst, int64_t dst_stride, const float* d_s
 int gsr_scene_reset_opacity(void* d_scene, int layout, int64_t n, float cap, float* d_m_opacity, float* d_v_opacity,
                             void* stream);
 
+/* ---- scene initialisation: a scene block from a point cloud ----
+ *
+ * The START of the training loop: what structure-from-motion gives, points with colours,
+ * becomes a scene block as 3DGS's create_from_pcd builds it — positions the points, SH dc from
+ * the colours, identity rotation, one opacity, and every scale the root of the mean squared
+ * distance to the point's three nearest neighbours.  That statistic is the only part that is
+ * not a fill; it has an entry point of its own and also runs on an existing block's positions.
+ * Both calls are context-free.
+ *
+ * 1. The statistic.  Coordinate c of point i is d_xyz[i * point_stride + c * comp_stride],
+ * strides in elements: (3, 1) is an interleaved [n, 3] array, (1, S) is planar with plane
+ * stride S (a scene block's own x, y, z arrays with S = the block's stride).
+ *
+ * The rule.  Everything is float32 with one rounding per operation and no FMA.
+ *   - A point is valid when its three coordinates are finite.  Let m be the number of valid
+ *     points.
+ *   - For valid i and valid j != i (j != i by index, so a coincident point is a neighbour at
+ *     distance 0): d2(i,j) = ((dx*dx) + (dy*dy)) + (dz*dz), with dx = x_j - x_i and so on.  The
+ *     expression is bitwise symmetric in (i, j).
+ *   - Let k = min(3, m - 1), and let b0 <= b1 <= b2 be the k smallest values of d2(i, .),
+ *     taken as a multiset.
+ *   - d_mean2[i] is ((b0 + b1) + b2) / 3.0f for k = 3; (b0 + b1) / 2.0f for k = 2; b0 for
+ *     k = 1; +0 for k = 0.
+ *   - A d2 that overflows to +inf is an ordinary value and propagates.
+ *   - An invalid point is nobody's neighbour.  Its d_mean2 is +0, and *d_bad (may be NULL; a
+ *     device word the caller zeroes) is incremented once per such point.
+ * The k smallest VALUES are unique whatever the search order, so the result is exact:
+ * reproducible bit for bit, independent of the launch shape, and equal to brute force.  The
+ * acceleration structure (a Morton order with 21 bits per axis, leaves of 64 points, two box
+ * levels above them) only sets the speed: a box is skipped only when its lower bound, formed by
+ * the same expression — per axis e = fmaxf(fmaxf(lo - q, q - hi), 0), then ((ex*ex) + (ey*ey))
+ * + (ez*ez) — is strictly greater than the third best so far.  Rounding is monotone, so that
+ * float32 bound never exceeds the float32 distance to a point inside the box.
+ *
+ * Stream-ordered; never allocates and never synchronises; all working memory is d_scratch
+ * (gsr_points_knn_scratch_bytes(n) bytes, about 32 n), and nothing is written past
+ * scratch_bytes or past d_mean2[n).  No atomics on the output; *d_bad and the bounds inside the
+ * scratch are integer atomics.
+ * gsr_points_knn_scratch_bytes: >= 0 and non-decreasing in n; negative (GSR_E_ARG) for n
+ * outside [0, INT32_MAX].
+ * GSR_E_ARG, before any device work: a NULL d_xyz, d_mean2 or d_scratch with n > 0; n outside
+ * [0, INT32_MAX]; a stride < 1; point_stride == comp_stride, or strides whose elements overlap
+ * for the given n (neither point_stride >= 3 * comp_stride nor comp_stride >= n *
+ * point_stride); scratch_bytes below gsr_points_knn_scratch_bytes(n); a pointer that is not
+ * 4-byte aligned.  n == 0 is GSR_OK without device work. */
+int64_t gsr_points_knn_scratch_bytes(int64_t n);
+int gsr_points_knn_dist2(const float* d_xyz, int64_t point_stride, int64_t comp_stride, int64_t n,
+                         float* d_mean2 /* n */, uint32_t* d_bad /* or NULL */, void* d_scratch, size_t scratch_bytes,
+                         void* stream);
+
+/* 2. The initialiser.  Returns a new scene block as gsr_scene_gather builds it (one hipMalloc;
+ * count n, stride rounded up to 64; free with gsr_scene_free; elements in [n, stride)
+ * unspecified); narrays is 38, 49 or 59; n == 0 gives a header-only block.  Per Gaussian, in
+ * float32 as written:
+ *   x, y, z    the point's bits (an invalid point's too: the caller prunes by d_bad / d_mean2)
+ *   opacity  = cfg->opacity
+ *   scale_c  = fminf(sqrtf(fmaxf(mean2, min_dist2)) * scale_mul, scale_max),  c = 0, 1, 2
+ *   rot      = (1, 0, 0, 0)
+ *   SH         dc of channel c = (rgb_c - 0.5f) / 0.28209479177387814f (the inverse of the
+ *              colour the preprocess forms; d_rgb NULL: 0.5 grey, dc = +0), at sh[c] of a 38- or
+ *              49-array block and sh[3 * 0 + c] of a 59-array block; every other SH plane +0;
+ *              non-finite colours propagate
+ *   a 49-array block adds trbf_center = t_center, trbf_scale = t_scale, motion +0
+ * mean2 is gsr_points_knn_dist2 of the points; d_mean2 (may be NULL; n floats) receives it,
+ * *d_bad (may be NULL) counts the invalid points.  Colour c of point i is d_rgb[i *
+ * rgb_point_stride + c * rgb_comp_stride].
+ * The header and the arrays are written on `stream`.  SYNCHRONOUS, like gsr_scene_densify:
+ * allocates the block and its own k-NN scratch, waits for `stream`, frees the scratch; called
+ * once per run.
+ * Returns NULL and sets gsr_last_error on failure.  GSR_E_ARG, before any device work: the
+ * cases of gsr_points_knn_dist2 (the rgb strides checked the same way when d_rgb is non-NULL);
+ * a bad narrays; a NULL cfg; a NaN field in cfg; opacity outside [GSR_ADAM_OPACITY_MIN,
+ * GSR_ADAM_OPACITY_MAX]; min_dist2 < 0; scale_mul <= 0 or not finite; scale_max <= 0; t_scale
+ * <= 0 on a 4D block; unknown flag bits. */
+typedef struct gsr_init_config {
+    float opacity;     /* stored opacity of every Gaussian (3DGS 0.1) */
+    float min_dist2;   /* floor on the mean squared distance (3DGS 1e-7) */
+    float scale_mul;   /* 1 */
+    float scale_max;   /* +inf: off (some trainers cap the initial scale by the scene extent) */
+    float t_center;    /* 4D blocks only: stored trbf_center */
+    float t_scale;     /* 4D blocks only: stored trbf_scale (> 0) */
+    int flags;         /* 0; unknown bits refused */
+} gsr_init_config;
+void* gsr_scene_from_points(const float* d_xyz, int64_t point_stride, int64_t comp_stride,
+                            const float* d_rgb /* or NULL: 0.5 grey */, int64_t rgb_point_stride,
+                            int64_t rgb_comp_stride, int64_t n, int narrays, const gsr_init_config* cfg,
+                            float* d_mean2 /* n, or NULL */, uint32_t* d_bad /* or NULL */, void* stream);
+
 /* ---- image loss: the step between gsr_render and gsr_render_backward_scene ----
  *
  * The LOSS of render -> LOSS -> gsr_render_backward_scene -> update: the 3DGS training loss
