@@ -28,13 +28,13 @@ $(OBJDIR)/%.o: $(SRCDIR)/%.hip $(HDRS) $(DEVHDRS)
 	mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
-$(OBJDIR)/%.o: $(SRCDIR)/%.cpp $(HDRS)
+$(OBJDIR)/%.o: $(SRCDIR)/%.cpp $(HDRS) $(SRCDIR)/gsr_host.h
 	mkdir -p $(OBJDIR)
 	$(HIPCC) $(HOSTFLAGS) -x c++ -D__HIP_PLATFORM_AMD__ -c $< -o $@
 
 $(OBJDIR)/gsr_gl.o: include/gsr_gl.h
 
-$(LIB): $(KOBJS) $(OBJDIR)/gsr_runtime.o $(OBJDIR)/gsr_ply.o $(OBJDIR)/gsr_gl.o
+$(LIB): $(KOBJS) $(OBJDIR)/gsr_runtime.o $(OBJDIR)/gsr_scene.o $(OBJDIR)/gsr_ply.o $(OBJDIR)/gsr_gl.o
 	mkdir -p $(dir $(LIB))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -ldl -Wl,-soname,libgsr.so
 

@@ -1,4 +1,4 @@
-// gsr_internal.h — shared between the host runtime (gsr_runtime.cpp) and the
+// gsr_internal.h — shared between the host runtime (gsr_runtime.cpp, gsr_scene.cpp) and the
 // gfx950 kernels (gsr_kernels.hip, gsr_bucket_sort.hip, gsr_blend.hip, gsr_blend_derived.hip,
 // gsr_scene_ops.hip, gsr_scene_densify.hip, gsr_scene_init.hip, gsr_scene_adam.hip, gsr_image_loss.hip, gsr_project.hip, gsr_probes.hip).  Not part of the public ABI.
 #pragma once
@@ -322,7 +322,7 @@ hipError_t launch_gather_planes(void* dst, int64_t dst_stride, const void* src, 
 hipError_t launch_scan_counts(uint32_t* counts, uint32_t chunks, hipStream_t s);
 
 // Scene densification (include/gsr.h "scene densification"; gsr_scene_densify.hip).  The host
-// has checked every argument (gsr_runtime.cpp); n == 0 (m == 0, n_out == 0) launches nothing.
+// has checked every argument (gsr_scene.cpp); n == 0 (m == 0, n_out == 0) launches nothing.
 // launch_densify_accumulate: the statistic, one thread per Gaussian.
 // launch_densify_count: per chunk of kDensifyChunk sources its output count into counts
 // (densify_chunks(n) + 1 words, then scanned in place: the chunks' first output positions, and
@@ -355,7 +355,7 @@ hipError_t launch_reset_opacity(float* arrays, int64_t stride, uint32_t n, float
                                 hipStream_t s);
 
 // Scene initialisation (include/gsr.h "scene initialisation"; gsr_scene_init.hip).  The host has
-// checked every argument (gsr_runtime.cpp).  launch_points_knn: the exact 3-NN statistic of n
+// checked every argument (gsr_scene.cpp).  launch_points_knn: the exact 3-NN statistic of n
 // points into mean2, all working memory in `scratch` (knn_scratch_bytes(n) bytes: the bounds,
 // two item buffers and the histograms of the sort, the sorted position planes, three box
 // levels); n == 0 launches nothing.  The structure's constants, which the tests straddle: a
@@ -379,7 +379,7 @@ hipError_t launch_scene_init_fill(void* block, int64_t stride, int narrays, cons
 // every active plane.  The plane table travels in the kernel arguments (the call never
 // allocates): per active plane the block array it steps, its gradient and moment planes, its
 // learning rate and how the stored value is stepped.  flags: GSR_ADAM_*; the host has
-// checked every argument (gsr_runtime.cpp).  n == 0 or no plane launches nothing.
+// checked every argument (gsr_scene.cpp).  n == 0 or no plane launches nothing.
 enum { kAdamPlain = 0, kAdamExp = 1, kAdamOpacity = 2 };   // x - d | x exp(-d) | the logit step
 struct AdamPlane {
     float* g;
@@ -403,7 +403,7 @@ hipError_t launch_scene_adam(float* arrays, int64_t stride, uint32_t n, const Ad
 // scratch, in floats: kLossSlotFloats of per-workgroup {sum |d|, sum d^2, sum SSIM} (the tiled
 // launches run at most kLossMaxGroups workgroups, each walking tiles), then, only with `grad`,
 // the three partial maps of 3 * W * H each.  The host has checked every argument, the scratch
-// size among them (gsr_runtime.cpp); c_* are grad_scale * weight / (3 W H), signed and doubled
+// size among them (gsr_scene.cpp); c_* are grad_scale * weight / (3 W H), signed and doubled
 // as the backward kernel adds them.
 constexpr int kLossMaxGroups = 2048;   // 8 workgroups of 256 threads for each of 256 CUs
 constexpr int64_t kLossSlotFloats = 3 * (int64_t)kLossMaxGroups;
