@@ -22,7 +22,7 @@ all: $(LIB) oracle
 
 # the kernel translation units (gfx950 device code + launch wrappers); a stage that gets a
 # file of its own is added here
-KOBJS = $(addprefix $(OBJDIR)/,gsr_kernels.o gsr_bucket_sort.o gsr_blend.o gsr_blend_derived.o gsr_scene_ops.o gsr_scene_densify.o gsr_scene_init.o gsr_scene_adam.o gsr_image_loss.o gsr_project.o gsr_probes.o)
+KOBJS = $(addprefix $(OBJDIR)/,gsr_kernels.o gsr_bucket_sort.o gsr_blend.o gsr_blend_derived.o gsr_scene_ops.o gsr_scene_densify.o gsr_scene_init.o gsr_scene_adam.o gsr_scene_pack.o gsr_image_loss.o gsr_project.o gsr_probes.o)
 
 $(OBJDIR)/%.o: $(SRCDIR)/%.hip $(HDRS) $(DEVHDRS)
 	mkdir -p $(OBJDIR)
@@ -34,7 +34,7 @@ $(OBJDIR)/%.o: $(SRCDIR)/%.cpp $(HDRS) $(SRCDIR)/gsr_host.h
 
 $(OBJDIR)/gsr_gl.o: include/gsr_gl.h
 
-$(LIB): $(KOBJS) $(OBJDIR)/gsr_runtime.o $(OBJDIR)/gsr_scene.o $(OBJDIR)/gsr_ply.o $(OBJDIR)/gsr_gl.o
+$(LIB): $(KOBJS) $(OBJDIR)/gsr_runtime.o $(OBJDIR)/gsr_scene.o $(OBJDIR)/gsr_scene_save.o $(OBJDIR)/gsr_ply.o $(OBJDIR)/gsr_gl.o
 	mkdir -p $(dir $(LIB))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -ldl -Wl,-soname,libgsr.so
 

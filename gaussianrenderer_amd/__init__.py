@@ -40,6 +40,7 @@ __all__ = [
     "densify_accumulate", "densify_gather_planes", "densify_normals", "DENSIFY_CHUNK",
     "points_knn_scratch_bytes", "points_knn_dist2", "InitConfig", "KNN_LEAF", "KNN_FAN", "KNN_BOUNDS_CHUNK",
     "KNN_SORT_TILE", "SH_C0",
+    "write_ply", "ply_row_floats", "raw_probe",
 ]
 
 # gsr_read_splats record (include/gsr.h).
@@ -122,6 +123,34 @@ def write_synthetic_ply(path: str, n: int, seed: int) -> None:
 def write_synthetic_ply4d(path: str, n: int, seed: int) -> None:
     """Seeded synthetic 4D (Spacetime-Gaussian style, 73-property) PLY for config 5."""
     check(lib().gsr_synth_write_ply4d(path.encode(), int(n), int(seed)), "gsr_synth_write_ply4d")
+
+
+def write_ply(path: str, soa: np.ndarray) -> None:
+    """A (38 | 49 | 59, n) float32 SoA, activated as read_ply and Scene.download give it, as a
+    3DGS .ply (gsr_ply_write_host): the inverse of read_ply, and byte for byte what
+    Scene.save_ply writes for the same values."""
+    soa = np.ascontiguousarray(soa, dtype=np.float32)
+    if soa.ndim != 2:
+        raise ValueError("write_ply: soa must be (narrays, n)")
+    check(lib().gsr_ply_write_host(str(path).encode(), soa.ctypes.data, soa.shape[0], soa.shape[1]),
+          "gsr_ply_write_host")
+
+
+def ply_row_floats(narrays: int) -> int:
+    """Floats per row of the .ply of a block with `narrays` arrays: 62, or 73 for a 4D block."""
+    p = int(lib().gsr_ply_row_floats(int(narrays)))
+    if p < 0:
+        raise GsrError(p, "gsr_ply_row_floats")
+    return p
+
+
+def raw_probe(x, kind: int) -> np.ndarray:
+    """gsr_raw_log (kind 0) or gsr_raw_logit (kind 1) of float32 values on the host: the raw
+    value the PLY writers store for a scale or an opacity."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.empty_like(x)
+    check(lib().gsr_raw_probe(x.ctypes.data, x.size, int(kind), out.ctypes.data), "gsr_raw_probe")
+    return out
 
 
 class Scene:
@@ -315,6 +344,29 @@ class Scene:
         check(lib().gsr_scene_reset_opacity(self.ptr or None, self.layout, self.n, float(cap),
                                             _dev_ptr(m_opacity_ptr) or None, _dev_ptr(v_opacity_ptr) or None,
                                             stream or None), "gsr_scene_reset_opacity")
+
+    def save_ply(self, path: str, chunk_rows: int = 0, stream: int = 0) -> None:
+        """This block as a 3DGS .ply (gsr_scene_save_ply, include/gsr.h "scene export"): the
+        inverse of from_ply, byte-identical to write_ply(path, self.download()).  The rows are
+        de-activated and interleaved on the device and streamed out in chunks of chunk_rows
+        rows (0: 65,536) through pinned buffers; the file appears under `path` only when it is
+        complete.  Synchronous on `stream`: work queued there before the call is in the file."""
+        if not self.ptr:
+            raise ValueError("Scene.save_ply: the scene has been freed")
+        check(lib().gsr_scene_save_ply(self.ptr, self.narrays, self.n, str(path).encode(), int(chunk_rows),
+                                       stream or None), "gsr_scene_save_ply")
+
+    def pack_rows(self, out_ptr, first: int, count: int, stream: int = 0) -> None:
+        """Rows [first, first + count) of this block in the .ply row format into the device
+        floats at out_ptr (count * ply_row_floats(narrays) of them; nothing past them is
+        written), stream-ordered (gsr_scene_pack_rows)."""
+        out = _dev_ptr(out_ptr)
+        if count > 0 and not out:
+            raise ValueError("Scene.pack_rows: out_ptr is missing")
+        if count > 0 and not self.ptr:
+            raise ValueError("Scene.pack_rows: the scene has been freed")
+        check(lib().gsr_scene_pack_rows(self.ptr or None, self.layout, self.n, int(first), int(count), out or None,
+                                        stream or None), "gsr_scene_pack_rows")
 
     def free(self):
         if self.ptr and self.owned:

@@ -325,6 +325,12 @@ SIGNATURES = [
     ("gsr_image_loss_scratch_bytes", c_int64, [c_int, c_int, c_int]),
     ("gsr_image_loss", c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(LossConfig), c_void_p, c_void_p, c_void_p,
                                c_int64, c_void_p]),
+    # scene export (include/gsr.h)
+    ("gsr_ply_row_floats", c_int64, [c_int]),
+    ("gsr_scene_pack_rows", c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    ("gsr_scene_save_ply", c_int, [c_void_p, c_int, c_int64, c_char_p, c_int64, c_void_p]),
+    ("gsr_ply_write_host", c_int, [c_char_p, c_void_p, c_int, c_int64]),
+    ("gsr_raw_probe", c_int, [c_void_p, c_int, c_int, c_void_p]),
     ("gsr_ply_read_host", c_int, [c_char_p, c_void_p, c_int64, POINTER(c_int64)]),
     ("gsr_ply_read_host_ex", c_int, [c_char_p, c_void_p, c_int, c_int64, POINTER(c_int64), c_int, POINTER(c_int)]),
     ("gsr_synth_write_ply", c_int, [c_char_p, c_int64, c_uint64]),

@@ -1,5 +1,5 @@
 // gsr_device.h — device helpers the gfx950 kernel translation units share (gsr_kernels.hip,
-// gsr_bucket_sort.hip, gsr_blend.hip, gsr_blend_derived.hip, gsr_scene_ops.hip, gsr_scene_densify.hip, gsr_scene_init.hip, gsr_image_loss.hip,
+// gsr_bucket_sort.hip, gsr_blend.hip, gsr_blend_derived.hip, gsr_scene_ops.hip, gsr_scene_densify.hip, gsr_scene_init.hip, gsr_scene_pack.hip, gsr_image_loss.hip,
 // gsr_project.hip, gsr_probes.hip): wave and workgroup
 // scans, ballot ranking, chunk and XCD mappings, the depth-sort pass plan, and the host-side
 // launch helpers.  Inline functions only: no kernels, no __constant__ data.  What only the

@@ -1,5 +1,5 @@
 // gsr_host.h — what the host translation units behind include/gsr.h share (gsr_runtime.cpp, the
-// frame pipeline; gsr_scene.cpp, the context-free scene API): the error macros, the owned device
+// frame pipeline; gsr_scene.cpp, the context-free scene API; gsr_scene_save.cpp, the scene export): the error macros, the owned device
 // allocation and a scene block's two facts of shape.  Host only: the host/kernel boundary is
 // gsr_internal.h.  The thread's message itself (gsr::set_error, gsr_last_error) lives in
 // gsr_runtime.cpp.
@@ -64,3 +64,7 @@ inline float* scene_arrays(void* d) { return reinterpret_cast<float*>(static_cas
 inline const float* scene_arrays(const void* d) {
     return reinterpret_cast<const float*>(static_cast<const char*>(d) + GSR_SCENE_HEADER_BYTES);
 }
+
+// A device scene block's header against (narrays, n) and its magic; GSR_OK, or GSR_E_ARG /
+// GSR_E_HIP with the message set, `who` naming the call (gsr_scene.cpp).
+int check_scene_block(const void* d_scene, int narrays, int64_t n, const char* who);

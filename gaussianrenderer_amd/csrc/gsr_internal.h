@@ -1,12 +1,14 @@
-// gsr_internal.h — shared between the host runtime (gsr_runtime.cpp, gsr_scene.cpp) and the
+// gsr_internal.h — shared between the host runtime (gsr_runtime.cpp, gsr_scene.cpp,
+// gsr_scene_save.cpp, gsr_ply.cpp) and the
 // gfx950 kernels (gsr_kernels.hip, gsr_bucket_sort.hip, gsr_blend.hip, gsr_blend_derived.hip,
-// gsr_scene_ops.hip, gsr_scene_densify.hip, gsr_scene_init.hip, gsr_scene_adam.hip, gsr_image_loss.hip, gsr_project.hip, gsr_probes.hip).  Not part of the public ABI.
+// gsr_scene_ops.hip, gsr_scene_densify.hip, gsr_scene_init.hip, gsr_scene_adam.hip, gsr_scene_pack.hip, gsr_image_loss.hip, gsr_project.hip, gsr_probes.hip).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <mutex>
+#include <string>
 
 #include "gsr_types.h"
 
@@ -397,6 +399,72 @@ struct AdamLaunch {
 };
 hipError_t launch_scene_adam(float* arrays, int64_t stride, uint32_t n, const AdamLaunch& L, uint32_t* bad,
                              hipStream_t s);
+
+// Scene export (include/gsr.h "scene export").  pack_map: the row format of a block kind as
+// a table, property p of a row <- block array array[p] under kind[p]; the host writer
+// (gsr_ply.cpp) and the pack kernel (gsr_scene_pack.hip) walk the same table.  nprops is 0
+// for a narrays that is no block kind.
+enum { kPackCopy = 0, kPackLog = 1, kPackLogit = 2, kPackZero = 3 };   // bits | gsr_raw_log | gsr_raw_logit | +0
+constexpr int kPackMaxProps = 73;
+struct PackMap {
+    uint8_t array[kPackMaxProps];
+    uint8_t kind[kPackMaxProps];
+    int nprops;
+};
+inline PackMap pack_map(int narrays) {
+    PackMap m{};
+    const bool four_d = narrays == GSR_SCENE4D_NARRAYS, sh3 = narrays == GSR_SCENE_SH3_NARRAYS;
+    if (narrays != GSR_SCENE_NARRAYS && !four_d && !sh3) return m;
+    int p = 0;
+    auto put = [&](int array, int kind) {
+        m.array[p] = (uint8_t)array;
+        m.kind[p++] = (uint8_t)kind;
+    };
+    for (int c = 0; c < 3; c++) put(GSR_A_X + c, kPackCopy);
+    for (int c = 0; c < 3; c++) put(0, kPackZero);   // nx ny nz
+    for (int c = 0; c < 3; c++) put(GSR_A_SH0 + c, kPackCopy);
+    for (int j = 0; j < 45; j++) {
+        if (sh3) put(GSR_A_SH0 + 3 * (1 + j % 15) + j / 15, kPackCopy);   // channel-major f_rest <- sh[3k + c]
+        else if (j < 24) put(GSR_A_SH0 + 3 + j, kPackCopy);
+        else put(0, kPackZero);   // f_rest_24..44: the block never held them
+    }
+    put(GSR_A_OPACITY, kPackLogit);
+    for (int c = 0; c < 3; c++) put(GSR_A_SCALE0 + c, kPackLog);
+    for (int c = 0; c < 4; c++) put(GSR_A_ROT0 + c, kPackCopy);
+    if (four_d) {
+        put(GSR_A_TCENTER, kPackCopy);
+        put(GSR_A_TSCALE, kPackLog);
+        for (int c = 0; c < 9; c++) put(GSR_A_MOTION0 + c, kPackCopy);
+    }
+    m.nprops = p;
+    return m;
+}
+// The pack kernel (k_scene_pack): rows [first, first + count) of the block's arrays as count *
+// nprops contiguous floats at `rows`, one workgroup per tile of kPackTileRows rows counted from
+// `first`.  The host has checked every argument (gsr_scene_save.cpp); count == 0 launches nothing.
+constexpr int kPackTileRows = 64;
+hipError_t launch_scene_pack(const float* arrays, int64_t stride, int narrays, uint32_t first, uint32_t count,
+                             float* rows, hipStream_t s);
+
+// The file side of both PLY writers (gsr_ply.cpp): the synthetic writers' header for n rows,
+// then whatever write() appends, in a temporary file beside `path` that commit() renames over
+// it.  Destroyed without a commit, it removes the temporary file and leaves `path` as it was.
+// Every failure returns GSR_E_IO with the message set (`who` names the call).
+class PlyFile {
+public:
+    PlyFile() = default;
+    PlyFile(const PlyFile&) = delete;
+    PlyFile& operator=(const PlyFile&) = delete;
+    ~PlyFile();
+    int open(const char* path, int64_t n, bool four_d, const char* who);
+    int write(const void* data, size_t bytes);
+    int commit();
+
+private:
+    int fd_ = -1;
+    std::string path_, tmp_;
+    const char* who_ = "";
+};
 
 // Image loss (gsr_image_loss; gsr_image_loss.hip): a tiled forward launch, a one-workgroup sum
 // of the loss values (only with `loss`) and a tiled backward launch (only with `grad`).

@@ -1,5 +1,6 @@
-// gsr_ply.cpp — host PLY loading into the SoA scene arrays, and the seeded
-// synthetic scene writers (SURVEY.md 8d, config 5 spec in DESIGN.md).
+// gsr_ply.cpp — host PLY loading into the SoA scene arrays, the seeded
+// synthetic scene writers (SURVEY.md 8d, config 5 spec in DESIGN.md), and the host side of
+// the scene export (gsr_ply_write_host and the PlyFile both PLY writers write through).
 //
 // Two modes:
 //   reference (flags 0): restates loadGaussianCudaFromPly (misc.cu:13-134) and
@@ -17,7 +18,12 @@
 // plus the Spacetime-Gaussian 4D properties (trbf_center, trbf_scale,
 // motion_0..8) into arrays 38..48 when the caller asks for 49 arrays, and
 // (GSR_PLY_SH3, 59 arrays) all 45 f_rest mapped channel-major -> sh[3k + c].
+#include <fcntl.h>
+#include <unistd.h>
+
 #include <algorithm>
+#include <atomic>
+#include <cerrno>
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
@@ -29,6 +35,7 @@
 #include <vector>
 
 #include "gsr.h"
+#include "gsr_detmath.h"
 #include "gsr_internal.h"
 
 using gsr::set_error;
@@ -446,10 +453,10 @@ extern "C" int gsr_ply_read_host(const char* path, float* soa, int64_t capacity,
 
 namespace {
 
-int write_synth(const char* path, int64_t n, uint64_t seed, bool four_d) {
-    if (!path || n < 0 || n > INT32_MAX) return set_error(GSR_E_ARG, "gsr_synth_write_ply: bad argument");
-    std::ofstream f(path, std::ios::binary);
-    if (!f) return set_error(GSR_E_IO, "cannot write %s", path);
+// The header of every .ply this library writes: the standard 62 3DGS properties as floats, plus
+// the 11 Spacetime-Gaussian ones of a 4D scene.
+std::string ply_header(int64_t n, bool four_d) {
+    std::ostringstream f;
     f << "ply\nformat binary_little_endian 1.0\nelement vertex " << n << "\n";
     const char* base[] = {"x", "y", "z", "nx", "ny", "nz", "f_dc_0", "f_dc_1", "f_dc_2"};
     for (const char* b : base) f << "property float " << b << "\n";
@@ -462,6 +469,14 @@ int write_synth(const char* path, int64_t n, uint64_t seed, bool four_d) {
         for (int r = 0; r < 9; r++) f << "property float motion_" << r << "\n";
     }
     f << "end_header\n";
+    return f.str();
+}
+
+int write_synth(const char* path, int64_t n, uint64_t seed, bool four_d) {
+    if (!path || n < 0 || n > INT32_MAX) return set_error(GSR_E_ARG, "gsr_synth_write_ply: bad argument");
+    std::ofstream f(path, std::ios::binary);
+    if (!f) return set_error(GSR_E_IO, "cannot write %s", path);
+    f << ply_header(n, four_d);
     const int nprop = four_d ? 73 : 62;
     std::mt19937_64 rng(seed);
     std::uniform_real_distribution<float> ux(-3.0f, 3.0f), uy(-1.7f, 1.7f), uz(-1.0f, 1.0f);
@@ -513,4 +528,96 @@ extern "C" int gsr_synth_write_ply(const char* path, int64_t n, uint64_t seed) {
 
 extern "C" int gsr_synth_write_ply4d(const char* path, int64_t n, uint64_t seed) {
     return write_synth(path, n, seed, true);
+}
+
+// ------------------------------------------------------------------ scene export (include/gsr.h)
+
+namespace gsr {
+
+PlyFile::~PlyFile() {
+    if (fd_ >= 0) ::close(fd_);
+    if (!tmp_.empty()) ::unlink(tmp_.c_str());
+}
+
+int PlyFile::open(const char* path, int64_t n, bool four_d, const char* who) {
+    who_ = who;
+    path_ = path;
+    // a fresh name beside the destination (rename() stays inside one file system)
+    static std::atomic<unsigned> serial{0};
+    for (int attempt = 0; attempt < 64 && fd_ < 0; attempt++) {
+        const std::string name = path_ + ".tmp." + std::to_string((long long)::getpid()) + "." +
+                                 std::to_string(serial.fetch_add(1));
+        fd_ = ::open(name.c_str(), O_WRONLY | O_CREAT | O_EXCL | O_CLOEXEC, 0666);
+        if (fd_ >= 0) tmp_ = name;
+        else if (errno != EEXIST) break;
+    }
+    if (fd_ < 0) return set_error(GSR_E_IO, "%s: cannot create a temporary file beside %s: %s", who_, path, std::strerror(errno));
+    const std::string h = ply_header(n, four_d);
+    return write(h.data(), h.size());
+}
+
+int PlyFile::write(const void* data, size_t bytes) {
+    const char* p = static_cast<const char*>(data);
+    while (bytes > 0) {
+        const ssize_t w = ::write(fd_, p, bytes);
+        if (w < 0 && errno == EINTR) continue;
+        if (w <= 0) return set_error(GSR_E_IO, "%s: write to %s failed: %s", who_, tmp_.c_str(), std::strerror(errno));
+        p += w;
+        bytes -= (size_t)w;
+    }
+    return GSR_OK;
+}
+
+int PlyFile::commit() {
+    const int rc = ::close(fd_);
+    fd_ = -1;
+    if (rc != 0) return set_error(GSR_E_IO, "%s: closing %s failed: %s", who_, tmp_.c_str(), std::strerror(errno));
+    if (::rename(tmp_.c_str(), path_.c_str()) != 0)
+        return set_error(GSR_E_IO, "%s: renaming %s to %s failed: %s", who_, tmp_.c_str(), path_.c_str(), std::strerror(errno));
+    tmp_.clear();
+    return GSR_OK;
+}
+
+}  // namespace gsr
+
+extern "C" int64_t gsr_ply_row_floats(int narrays) {
+    const int p = gsr::pack_map(narrays).nprops;
+    if (p == 0) return set_error(GSR_E_ARG, "gsr_ply_row_floats: narrays = %d", narrays);
+    return p;
+}
+
+extern "C" int gsr_raw_probe(const float* host_in, int n, int kind, float* host_out) {
+    if (!host_in || !host_out || n < 0 || (kind != 0 && kind != 1)) return set_error(GSR_E_ARG, "gsr_raw_probe: bad argument");
+    for (int i = 0; i < n; i++) host_out[i] = kind ? gsr_raw_logit(host_in[i]) : gsr_raw_log(host_in[i]);
+    return GSR_OK;
+}
+
+extern "C" int gsr_ply_write_host(const char* path, const float* host_soa, int narrays, int64_t n) {
+    const char* who = "gsr_ply_write_host";
+    if (!path || !host_soa) return set_error(GSR_E_ARG, "%s: null pointer", who);
+    const gsr::PackMap map = gsr::pack_map(narrays);
+    if (map.nprops == 0) return set_error(GSR_E_ARG, "%s: narrays = %d", who, narrays);
+    if (n < 0 || n > INT32_MAX) return set_error(GSR_E_ARG, "%s: n = %lld out of range", who, (long long)n);
+    gsr::PlyFile file;
+    if (int rc = file.open(path, n, narrays == GSR_SCENE4D_NARRAYS, who)) return rc;
+    // chunk by chunk; inside a chunk plane by plane, so what a property reads and how it is
+    // de-activated is decided once per 4,096 values and the loops are plain strided copies
+    const int P = map.nprops;
+    const int64_t chunk = 4096;
+    std::vector<float> rows((size_t)std::min(chunk, n) * (size_t)P);
+    for (int64_t i0 = 0; i0 < n; i0 += chunk) {
+        const int64_t m = std::min(chunk, n - i0);
+        for (int p = 0; p < P; p++) {
+            const float* src = host_soa + (size_t)map.array[p] * (size_t)n + (size_t)i0;
+            float* dst = rows.data() + p;
+            switch (map.kind[p]) {
+            case gsr::kPackCopy: for (int64_t r = 0; r < m; r++) dst[r * P] = src[r]; break;
+            case gsr::kPackLog: for (int64_t r = 0; r < m; r++) dst[r * P] = gsr_raw_log(src[r]); break;
+            case gsr::kPackLogit: for (int64_t r = 0; r < m; r++) dst[r * P] = gsr_raw_logit(src[r]); break;
+            default: for (int64_t r = 0; r < m; r++) dst[r * P] = 0.0f; break;
+            }
+        }
+        if (int rc = file.write(rows.data(), (size_t)m * (size_t)P * sizeof(float))) return rc;
+    }
+    return file.commit();
 }

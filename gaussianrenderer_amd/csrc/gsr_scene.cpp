@@ -148,8 +148,9 @@ extern "C" int gsr_gather_planes(void* d_dst, int64_t dst_stride, const void* d_
 }
 
 // The source block's header against (narrays, n), as gsr_scene_copy checks it, and its magic
-// (an AoS array is refused).  Synchronous 256-byte read.
-static int check_scene_block(const void* d_scene, int narrays, int64_t n, const char* who) {
+// (an AoS array is refused).  Synchronous 256-byte read.  (Declared in gsr_host.h: gsr_scene_save.cpp
+// checks its source with it too.)
+int check_scene_block(const void* d_scene, int narrays, int64_t n, const char* who) {
     gsr_scene_header h{};
     hipError_t e = hipMemcpy(&h, d_scene, sizeof h, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return set_err(GSR_E_HIP, "%s: reading the header failed: %s", who, hipGetErrorString(e));

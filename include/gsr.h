@@ -1101,6 +1101,60 @@ int gsr_image_loss(const float* d_image, const float* d_target, int W, int H, co
                    float* d_loss /* GSR_LOSS_NVALUES device floats, OVERWRITTEN, or NULL */,
                    void* d_scratch, int64_t scratch_bytes, void* stream);
 
+/* ---- scene export: a scene block as a 3DGS .ply, the inverse of the loader ----
+ *
+ * The way out of the loop that gsr_scene_from_points / the loaders open: a block that was
+ * trained, pruned or densified on the device becomes a file that gsr_load_ply_device, the
+ * reference viewer's loadGaussiansFromPly or any 3DGS tool reads.
+ *
+ * The row format.  One Gaussian is one row of P = gsr_ply_row_floats(narrays) little-endian
+ * floats: 62 for 38- and 59-array blocks, 73 for 49-array (4D) blocks, in the order of the header
+ * gsr_synth_write_ply* writes:
+ *   x y z | nx ny nz | f_dc_0..2 | f_rest_0..44 | opacity | scale_0..2 | rot_0..3
+ *   4D only: | trbf_center | trbf_scale | motion_0..8
+ * and the values are the inverse of the loader's store(), per block kind:
+ *   x y z, rot_*, trbf_center, motion_*    the stored bits (NaN payloads included)
+ *   nx ny nz                               +0
+ *   opacity                                gsr_raw_logit(stored)          (gsr_detmath.h)
+ *   scale_c, trbf_scale                    gsr_raw_log(stored)
+ *   f_dc_c                                 sh[c]
+ *   f_rest_j, 38- and 49-array blocks      sh[3 + j] for j < 24, +0 for j = 24..44 (never loaded)
+ *   f_rest_j, 59-array blocks              sh[3 (1 + j % 15) + j / 15]    (channel-major again)
+ * gsr_raw_log / gsr_raw_logit round alike on the host and the device, so gsr_ply_write_host of a
+ * download and gsr_scene_save_ply of the block write the same bytes.  A reload reproduces every
+ * copied array bit for bit and the opacity and the scales to the loader's own rounding (the raw
+ * functions' error bounds: gsr_detmath.h); a stored opacity of 0 or 1 and a stored scale of 0 or
+ * +inf come back as themselves through -inf / +inf, anything the loader cannot have produced
+ * (negative, NaN, an opacity above 1) as NaN.
+ *
+ * Both writers (gsr_scene_save_ply here, gsr_ply_write_host under "host helpers") write the
+ * header, then n * P floats (n == 0: the header alone), into a temporary file in the
+ * destination's directory and rename it over `path` only on success: on any failure they
+ * return GSR_E_IO or GSR_E_HIP, remove the temporary file and leave an existing `path` as it
+ * was.  Before any file or device work they refuse with GSR_E_ARG a NULL pointer, a narrays
+ * that is no block kind, n outside [0, INT32_MAX] and chunk_rows < 0. */
+
+/* Floats per row of the .ply for a block of `narrays` arrays (62 or 73), or GSR_E_ARG. */
+int64_t gsr_ply_row_floats(int narrays);
+/* Rows [first, first + count) of the block in the row format, row `first` at d_rows[0]: count *
+ * P device floats, and nothing past them is written.  Stream-ordered: no allocation, no wait;
+ * (layout, n) are trusted as gsr_scene_adam_step trusts them.  Only [0, n) of an array is read.
+ * The stores are 16 B wide when d_rows is 16-B aligned (any hipMalloc is), 4 B otherwise.
+ * GSR_E_ARG: the AoS layout or an unknown one, first < 0, count < 0, first + count > n, n outside
+ * [0, INT32_MAX], a NULL pointer with count > 0, a pointer off a 4-byte boundary.  count == 0
+ * is GSR_OK without device work. */
+int gsr_scene_pack_rows(const void* d_scene, int layout, int64_t n, int64_t first, int64_t count,
+                        float* d_rows, void* stream);
+/* The whole block into the file `path`.  The block's header is checked against (narrays, n) as
+ * gsr_scene_copy does (read synchronously); the block itself is only read.  Chunks of
+ * chunk_rows rows (0: the default, 65,536) are packed on `stream` into one of two device
+ * staging buffers and copied from there into one of two pinned host buffers, and chunk k - 1
+ * goes to the file while chunk k is in flight, so a save is bound by the disk.  SYNCHRONOUS on
+ * `stream`: work queued on it before the call (an Adam step) is in the file, and the call
+ * allocates and frees its four buffers (2 * chunk_rows * P * 4 bytes of each kind). */
+int gsr_scene_save_ply(const void* d_scene, int narrays, int64_t n, const char* path,
+                       int64_t chunk_rows, void* stream);
+
 /* ---------------------------------------------------------------- host helpers */
 
 /* PLY reader with the semantics of loadGaussianCudaFromPly (misc.cu:13-134 +
@@ -1113,6 +1167,16 @@ int gsr_ply_read_host(const char* path, float* host_soa, int64_t capacity, int64
  * properties. */
 int gsr_ply_read_host_ex(const char* path, float* host_soa, int narrays, int64_t capacity, int64_t* n_out,
                          int flags, int* is_4d);
+
+/* PLY writer, the inverse of gsr_ply_read_host_ex ("scene export" above has the row format and
+ * what both writers share): host_soa holds narrays (38, 49 or 59) arrays of n floats as
+ * gsr_scene_download gives them, activated.  Byte-identical to gsr_scene_save_ply of a block
+ * with the same values. */
+int gsr_ply_write_host(const char* path, const float* host_soa, int narrays, int64_t n);
+/* gsr_raw_log (kind 0) or gsr_raw_logit (kind 1) of gsr_detmath.h over n host floats: the raw
+ * values the writers store for a scale and an opacity.  GSR_E_ARG: a NULL pointer, n < 0,
+ * another kind. */
+int gsr_raw_probe(const float* host_in, int n, int kind, float* host_out);
 
 /* Seeded synthetic scene: writes a standard 62-property
  * binary_little_endian 3DGS .ply, or fills raw (pre-activation) property

@@ -360,6 +360,42 @@ GSR_HD float gsr_logf(float x) {
 }
 
 /*
+ * The raw (pre-activation) values a 3DGS .ply stores, from the activated values a scene block
+ * holds: the inverses of the loader's exp and sigmoid (gsr_ply.cpp store()), for the PLY writers
+ * (gsr_ply_write_host on the host, k_scene_pack on the device).  gsr_logf and plain float
+ * operations only, one rounding each, so both writers produce the same bits.
+ *
+ * gsr_raw_log(s): NaN or s < 0 -> the quiet NaN 0x7fc00000; +-0 -> -inf; +inf -> +inf; a
+ * subnormal s is scaled by 2^24 (exact) into the normal range and 24 ln 2 taken off again.
+ * Measured against double precision, one value per mantissa step of 2^-12 in every binade
+ * from the smallest subnormal to FLT_MAX (tests/test_ply_write.py): <= 0.722 ulp over the
+ * normal floats (gsr_logf's <= 2 ulp was only ever swept over (0, 1]), <= 1.006 ulp over the
+ * subnormal ones, which pay the subtraction's rounding too.  The test asserts 2 ulp.
+ *
+ * gsr_raw_logit(o) = log(o) - log(1 - o): NaN or o outside [0, 1] -> the quiet NaN; +-0 ->
+ * -inf; 1 -> +inf; exactly 0 at 0.5 (1 - 0.5 is exact and both logs are the same value).
+ * Over every o = k 2^-24, k = 1 .. 2^24 - 1 (1 - o is then exact), the bound is ABSOLUTE: the
+ * two logs' errors (2 ulp of each asserted) plus half an ulp of the result.  Measured: 0.453 of
+ * that bound, 1.373 ulp of the larger log, 9.6e-7 at most (at the ends, where the result is
+ * +-16.6); near 0.5 the result is small against its terms and an error of a few 1e-8 is many
+ * ulp of the result.
+ */
+GSR_HD float gsr_raw_log(float s) {
+    if (s != s || s < 0.0f) return gsr_bits_to_float(0x7fc00000u);
+    if (s == 0.0f) return -INFINITY;
+    if (s == INFINITY) return INFINITY;
+    if (s < 1.17549435e-38f) return gsr_logf(s * 16777216.0f) - 16.635532f;   /* 24 ln 2 */
+    return gsr_logf(s);
+}
+
+GSR_HD float gsr_raw_logit(float o) {
+    if (o != o || o < 0.0f || o > 1.0f) return gsr_bits_to_float(0x7fc00000u);
+    if (o == 0.0f) return -INFINITY;
+    if (o == 1.0f) return INFINITY;
+    return gsr_raw_log(o) - gsr_raw_log(1.0f - o);
+}
+
+/*
  * Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3",
  * SC11; the Random123 generator): ten rounds of two 32 x 32 -> 64 multiplies on a 128-bit
  * counter under a 64-bit key bumped by the Weyl constants between rounds.  The published

@@ -31,7 +31,7 @@ $(OUT)/%.o: $(SRC)/%.cpp $(HDRS) $(SRC)/gsr_host.h
 	mkdir -p $(OUT)
 	$(HIPCC) $(HOSTFLAGS) $(SAN) -x c++ -c $< -o $@
 
-$(OUT)/libgsr.so: $(KOBJS) $(OUT)/gsr_runtime.o $(OUT)/gsr_scene.o $(OUT)/gsr_ply.o $(OUT)/gsr_gl.o
+$(OUT)/libgsr.so: $(KOBJS) $(OUT)/gsr_runtime.o $(OUT)/gsr_scene.o $(OUT)/gsr_scene_save.o $(OUT)/gsr_ply.o $(OUT)/gsr_gl.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
 	    -shared-libsan -o $@ $^ -ldl -Wl,-soname,libgsr.so
 
