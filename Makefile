@@ -28,13 +28,17 @@ $(OBJDIR)/%.o: $(SRCDIR)/%.hip $(HDRS) $(DEVHDRS)
 	mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
-$(OBJDIR)/%.o: $(SRCDIR)/%.cpp $(HDRS) $(SRCDIR)/gsr_host.h
+$(OBJDIR)/%.o: $(SRCDIR)/%.cpp $(HDRS) $(SRCDIR)/gsr_host.h $(SRCDIR)/gsr_context.h
 	mkdir -p $(OBJDIR)
 	$(HIPCC) $(HOSTFLAGS) -x c++ -D__HIP_PLATFORM_AMD__ -c $< -o $@
 
 $(OBJDIR)/gsr_gl.o: include/gsr_gl.h
 
-$(LIB): $(KOBJS) $(OBJDIR)/gsr_runtime.o $(OBJDIR)/gsr_scene.o $(OBJDIR)/gsr_scene_save.o $(OBJDIR)/gsr_ply.o $(OBJDIR)/gsr_gl.o
+# the host translation units (gsr_context.h is private to the three that work on a context; the
+# rule above rebuilds every host file when it changes, which costs a few seconds)
+HOBJS = $(addprefix $(OBJDIR)/,gsr_runtime.o gsr_path.o gsr_inspect.o gsr_compat.o gsr_camera.o gsr_scene.o gsr_scene_save.o gsr_ply.o gsr_gl.o)
+
+$(LIB): $(KOBJS) $(HOBJS)
 	mkdir -p $(dir $(LIB))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -ldl -Wl,-soname,libgsr.so
 

@@ -1,5 +1,5 @@
-// gsr_internal.h — shared between the host runtime (gsr_runtime.cpp, gsr_scene.cpp,
-// gsr_scene_save.cpp, gsr_ply.cpp) and the
+// gsr_internal.h — shared between the host runtime (gsr_runtime.cpp, gsr_path.cpp, gsr_inspect.cpp,
+// gsr_compat.cpp, gsr_scene.cpp, gsr_scene_save.cpp, gsr_ply.cpp) and the
 // gfx950 kernels (gsr_kernels.hip, gsr_bucket_sort.hip, gsr_blend.hip, gsr_blend_derived.hip,
 // gsr_scene_ops.hip, gsr_scene_densify.hip, gsr_scene_init.hip, gsr_scene_adam.hip, gsr_scene_pack.hip, gsr_image_loss.hip, gsr_project.hip, gsr_probes.hip).  Not part of the public ABI.
 #pragma once
@@ -494,12 +494,12 @@ hipError_t launch_exp_probe(uint32_t key_lo, uint32_t key_hi, float x_big, unsig
                             hipStream_t s);
 hipError_t launch_xs_probe(const float* op, int n, float* out, hipStream_t s);
 
-// Drop-in frame into a device image on the drop-in context (gsr_runtime.cpp);
+// Drop-in frame into a device image on the drop-in context (gsr_compat.cpp);
 // callers hold dropin_mutex().  `what` names the failing step for the message.
 int dropin_render_device(gsr_gaussian* d_gaussians, int num_gaussians, const gsr_camera& cam, int num_tile_y,
                          int num_tile_x, int width_stride, int height_stride, int W, int H, float k,
                          float* d_out, const char** what);
 std::mutex& dropin_mutex();
-const char* last_error();
+const char* last_error();   // the thread's message, as gsr_last_error reads it (gsr_runtime.cpp)
 
 }  // namespace gsr

@@ -27,7 +27,7 @@
  *
  * tanf is NOT restated here: fx/fy (render.cu:620-621) are computed once per
  * frame on the host as a correctly rounded float tan (see gsr_camera_intrinsics
- * in gsr_runtime.cpp) and passed to the kernels, so both sides share them.
+ * in gsr_camera.cpp) and passed to the kernels, so both sides share them.
  */
 #ifndef GSR_DETMATH_H
 #define GSR_DETMATH_H

@@ -405,3 +405,85 @@ def test_two_aux_frames_give_identical_bytes(gpu, torch, c1, scene1):
     b = aux(gpu, torch, scene1, cam, W, H, feats=feats, renderer=r)
     for k in a:
         assert a[k].tobytes() == b[k].tobytes(), k
+
+
+# ---------------------------------------------------------------- 9. a workspace that grows in a live context
+
+def test_workspace_regrows(gpu, torch, tmp_path_factory):
+    """One context, no gsr_reserve: 500 Gaussians on 64 x 48, then 3,000 on 160 x 96 (past the
+    1,024-element floor of the per-Gaussian buffers, and a larger tile grid), then the small size
+    again.  At each step a plain frame, an aux frame with depth and 6 features (aux_z and
+    aux_pack), the fused backward call without a caller's scratch (rec_grads), an AoS-layout frame
+    (soa_tmp) and a frame with the depth split forced on (tbuf, bflag).  Each result equals, bit
+    for bit, the same call on a fresh context at that size.
+
+    The backward call's upstream gradient is non-zero at two pixels only: the blend's backward
+    pass sums a Gaussian's record gradients over pixels with float atomics in no fixed order, and
+    a sum of at most two terms is the same in either order, so the comparison can be exact."""
+    from gaussianrenderer_amd import _native
+    from test_gpu_parity import aos_records
+    sizes = {"small": (500, 64, 48), "large": (3000, 160, 96)}
+    data = {}
+    for name, (n, W, H) in sizes.items():
+        soa = scene_soa(gpu, tmp_path_factory, n, 3)[1]
+        data[name] = dict(n=n, W=W, H=H, cam=cam_for(gpu, W, H), scene=gpu.Scene.from_soa(soa),
+                          aos=torch.from_numpy(aos_records(soa)).cuda(),
+                          feats=np.random.default_rng(n).uniform(-3.0, 3.0, (6, n)).astype(np.float32))
+
+    def synced(r, call):
+        for _ in range(3):
+            call()
+            if r.sync() == 0:
+                return
+        raise AssertionError("frame still incomplete after three renders")
+
+    def image(r, d, **kw):
+        out = torch.full((3, d["H"], d["W"]), float("nan"), dtype=torch.float32, device="cuda")
+        scene = kw.pop("scene", d["scene"])
+        synced(r, lambda: r.render(scene, d["cam"], d["W"], d["H"], out.data_ptr(), **kw))
+        return {"out": out.cpu().numpy()}
+
+    def backward(r, d):
+        n = d["n"]
+        planes = {k: torch.zeros(c * n, dtype=torch.float32, device="cuda")
+                  for k, c in (("position", 3), ("opacity", 1), ("scale", 3), ("rot", 4), ("sh", 27))}
+
+        def call():
+            for p in planes.values():
+                p.zero_()
+            r.render_backward_scene(d["scene"], d["cam"], d["W"], d["H"], grad_image_ptr=d["grad"],
+                                    **{k + "_ptr": p for k, p in planes.items()})
+        synced(r, call)
+        got = {k: p.cpu().numpy() for k, p in planes.items()}
+        assert got["position"].any() and got["sh"].any()
+        return got
+
+    def split(r, d):
+        r.set_tuning(KNOB_SPLIT, 1)
+        got = image(r, d)
+        r.set_tuning(KNOB_SPLIT, 2)
+        return got
+
+    for d in data.values():   # the upstream gradient: the image's two brightest pixels, so splats cover them
+        img = image(gpu.Renderer(), d)["out"].sum(0)
+        g = np.zeros((3, d["H"], d["W"]), np.float32)
+        for px, v in zip(np.argsort(img, axis=None)[-2:], ((1.0, -0.5, 0.25), (-0.75, 1.0, 0.5))):
+            g[:, px // d["W"], px % d["W"]] = v
+        d["grad"] = torch.from_numpy(g).cuda()
+
+    calls = {
+        "render": image,
+        "aux": lambda r, d: aux(gpu, torch, d["scene"], d["cam"], d["W"], d["H"], feats=d["feats"], renderer=r),
+        "backward": backward,
+        "aos": lambda r, d: image(r, d, scene=d["aos"].data_ptr(), layout=_native.LAYOUT_AOS, n=d["n"]),
+        "split": split,
+    }
+    fresh = {(name, k): call(gpu.Renderer(), d) for name, d in data.items() for k, call in calls.items()}
+    assert (fresh["large", "render"]["out"] != 0).sum() > 1000
+    live = gpu.Renderer()
+    for name in ("small", "large", "small"):
+        for k, call in calls.items():
+            got, want = call(live, data[name]), fresh[name, k]
+            assert set(got) == set(want)
+            for plane in got:
+                assert same_bits(got[plane], want[plane]), (name, k, plane)

@@ -27,11 +27,13 @@ HDRS = include/gsr.h include/gsr_types.h include/gsr_detmath.h $(SRC)/gsr_intern
 
 all: $(OUT)/libgsr.so $(OUT)/liboracle.so
 
-$(OUT)/%.o: $(SRC)/%.cpp $(HDRS) $(SRC)/gsr_host.h
+$(OUT)/%.o: $(SRC)/%.cpp $(HDRS) $(SRC)/gsr_host.h $(SRC)/gsr_context.h
 	mkdir -p $(OUT)
 	$(HIPCC) $(HOSTFLAGS) $(SAN) -x c++ -c $< -o $@
 
-$(OUT)/libgsr.so: $(KOBJS) $(OUT)/gsr_runtime.o $(OUT)/gsr_scene.o $(OUT)/gsr_scene_save.o $(OUT)/gsr_ply.o $(OUT)/gsr_gl.o
+HOBJS = $(addprefix $(OUT)/,gsr_runtime.o gsr_path.o gsr_inspect.o gsr_compat.o gsr_camera.o gsr_scene.o gsr_scene_save.o gsr_ply.o gsr_gl.o)
+
+$(OUT)/libgsr.so: $(KOBJS) $(HOBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
 	    -shared-libsan -o $@ $^ -ldl -Wl,-soname,libgsr.so
 
