@@ -23,7 +23,7 @@ import numpy as np
 from . import _native
 from ._native import (AUX_MAX_FEATURES, AuxTargets, BackwardTargets, CONTRIB_WEIGHT_ONE, Camera, ContribTargets, GsrError, LAYOUT_AOS, LAYOUT_SCENE_BLOCK, LAYOUT_SCENE_BLOCK_4D,
                       LAYOUT_SCENE_BLOCK_SH3, NUM_STAGES, PLY_SH3, PLY_TYPED, SCENE4D_NARRAYS, SCENE_NARRAYS,
-                      SCENE_SH3_NARRAYS, RecordGrads, SceneGrads,
+                      SCENE_SH3_NARRAYS, RecordGrads, SceneGrads, AuxUpstream, RecordGradsAux, RecordGradsAuxOut,
                       ADAM_OPACITY_MAX, ADAM_OPACITY_MIN, ADAM_SKIP_ZERO, ADAM_ZERO_GRADS, AdamConfig,
                       LOSS_NVALUES, LossConfig, DENSIFY_CHUNK,
                       InitConfig, KNN_BOUNDS_CHUNK, KNN_FAN, KNN_LEAF, KNN_SORT_TILE, SH_C0,
@@ -34,7 +34,7 @@ __all__ = [
     "loadGaussianCudaFromPly", "preprocessCUDAGaussians", "read_ply", "write_synthetic_ply",
     "SPLAT_DTYPE", "STAGES", "TILE_PX", "lib", "AUX_MAX_FEATURES", "DisplayTarget", "display_gl_current", "preprocessCUDAGaussiansGL",
     "CONTRIB_WEIGHT_ONE", "ContribTargets", "BackwardTargets", "mask_indices", "gather_planes",
-    "RecordGrads", "SceneGrads",
+    "RecordGrads", "SceneGrads", "AuxUpstream", "RecordGradsAux", "RecordGradsAuxOut",
     "AdamConfig", "ADAM_SKIP_ZERO", "ADAM_ZERO_GRADS", "ADAM_OPACITY_MIN", "ADAM_OPACITY_MAX", "SCENE_GRAD_GROUPS",
     "LossConfig", "LOSS_NVALUES", "image_loss", "image_loss_scratch_bytes",
     "densify_accumulate", "densify_gather_planes", "densify_normals", "DENSIFY_CHUNK",
@@ -826,6 +826,109 @@ class Renderer:
                                              _dev_ptr(scratch_ptr) or None, byref(sg), stream or None)
         if rc not in (_native.GSR_OK, _native.GSR_E_OVERFLOW):
             raise GsrError(rc, "gsr_render_backward_scene")
+        return rc
+
+    def _aux_upstream(self, who, grad_image_ptr, grad_alpha_ptr, grad_depth_ptr, grad_feat_ptr, features_ptr, nfeat,
+                      feat_out) -> AuxUpstream:
+        """The prechecks the three *_aux calls share, and their gsr_aux_upstream."""
+        ups = [_dev_ptr(p) for p in (grad_image_ptr, grad_alpha_ptr, grad_depth_ptr, grad_feat_ptr)]
+        feats = _dev_ptr(features_ptr)
+        if not any(ups):
+            raise ValueError(f"{who}: no upstream gradient given")
+        if not 0 <= nfeat <= AUX_MAX_FEATURES:
+            raise ValueError(f"{who}: nfeat {nfeat} out of range [0, {AUX_MAX_FEATURES}]")
+        if nfeat > 0 and not feats:
+            raise ValueError(f"{who}: nfeat {nfeat} needs features_ptr")
+        if nfeat == 0 and (ups[3] or feat_out):
+            raise ValueError(f"{who}: feature gradients given with nfeat 0")
+        return AuxUpstream(*[p or None for p in ups], feats or None, nfeat)
+
+    def render_backward_aux(self, scene, cam: Camera, W: int, H: int, grad_image_ptr=None, grad_alpha_ptr=None,
+                            grad_depth_ptr=None, grad_feat_ptr=None, features_ptr=None, nfeat: int = 0,
+                            color_ptr=None, opacity_ptr=None, conic_ptr=None, center_ptr=None, z_ptr=None,
+                            feat_grad_ptr=None, k: float = 3.0, tiling=None, stream: int = 0,
+                            layout: int = LAYOUT_SCENE_BLOCK, n: int | None = None, time: float | None = None) -> int:
+        """render_backward with render_aux's depth and feature planes (gsr_render_backward_aux,
+        include/gsr.h).  Further inputs: grad_depth_ptr W*H (dL/d the un-normalised depth plane),
+        grad_feat_ptr nfeat*W*H planar (dL/d the feature planes) and features_ptr, the nfeat arrays
+        of n floats render_aux composites.  Further outputs, ACCUMULATED: z_ptr n floats (dL/d -Z)
+        and feat_grad_ptr nfeat planes of n (dL/d the feature values).  At least one input and one
+        output; an output whose upstream is missing is not touched.  Same returns as render()."""
+        outs = [_dev_ptr(p) for p in (color_ptr, opacity_ptr, conic_ptr, center_ptr, z_ptr, feat_grad_ptr)]
+        up = self._aux_upstream("render_backward_aux", grad_image_ptr, grad_alpha_ptr, grad_depth_ptr, grad_feat_ptr,
+                                features_ptr, nfeat, outs[5])
+        if not any(outs):
+            raise ValueError("render_backward_aux: no output requested")
+        ptr = scene.ptr if isinstance(scene, Scene) else int(scene)
+        n = scene.n if n is None else n
+        if isinstance(scene, Scene) and layout == LAYOUT_SCENE_BLOCK:
+            layout = scene.layout
+        if time is not None:
+            self.set_time(time)
+        t = tiling or TilingInformation(1, 1, H, W)
+        rg = RecordGradsAuxOut(*[o or None for o in outs])
+        rc = lib().gsr_render_backward_aux(self.ctx, ptr, layout, n, byref(cam), W, H, t.num_tile_x, t.num_tile_y,
+                                           t.width_stride, t.height_stride, k, byref(up), byref(rg), stream or None)
+        if rc not in (_native.GSR_OK, _native.GSR_E_OVERFLOW):
+            raise GsrError(rc, "gsr_render_backward_aux")
+        return rc
+
+    def project_backward_aux(self, scene, cam: Camera, W: int, H: int, d_color_ptr=None, d_opacity_ptr=None,
+                             d_conic_ptr=None, d_center_ptr=None, d_z_ptr=None, position_ptr=None, opacity_ptr=None,
+                             scale_ptr=None, rot_ptr=None, sh_ptr=None, temporal_ptr=None, k: float = 3.0,
+                             stream: int = 0, layout: int = LAYOUT_SCENE_BLOCK, n: int | None = None,
+                             time: float | None = None) -> int:
+        """project_backward with an eleventh upstream entry (gsr_project_backward_aux,
+        include/gsr.h): d_z_ptr, n floats, render_backward_aux's z_ptr (dL/d -Z), carried on to the
+        position and, in a 4D scene, the temporal arrays.  Everything else as project_backward."""
+        ins = [_dev_ptr(p) for p in (d_color_ptr, d_opacity_ptr, d_conic_ptr, d_center_ptr, d_z_ptr)]
+        outs = [_dev_ptr(p) for p in (position_ptr, opacity_ptr, scale_ptr, rot_ptr, sh_ptr, temporal_ptr)]
+        if not any(ins):
+            raise ValueError("project_backward_aux: no upstream gradient given")
+        if not any(outs):
+            raise ValueError("project_backward_aux: no output requested")
+        ptr = scene.ptr if isinstance(scene, Scene) else int(scene)
+        n = scene.n if n is None else n
+        if isinstance(scene, Scene) and layout == LAYOUT_SCENE_BLOCK:
+            layout = scene.layout
+        if time is not None:
+            self.set_time(time)
+        rg = RecordGradsAux(*[p or None for p in ins])
+        sg = SceneGrads(*[p or None for p in outs])
+        check(lib().gsr_project_backward_aux(self.ctx, ptr, layout, n, byref(cam), W, H, k, byref(rg), byref(sg),
+                                             stream or None), "gsr_project_backward_aux")
+        return _native.GSR_OK
+
+    def render_backward_scene_aux(self, scene, cam: Camera, W: int, H: int, grad_image_ptr=None, grad_alpha_ptr=None,
+                                  grad_depth_ptr=None, grad_feat_ptr=None, features_ptr=None, nfeat: int = 0,
+                                  feat_grad_ptr=None, scratch_ptr=None, position_ptr=None, opacity_ptr=None,
+                                  scale_ptr=None, rot_ptr=None, sh_ptr=None, temporal_ptr=None, k: float = 3.0,
+                                  tiling=None, stream: int = 0, layout: int = LAYOUT_SCENE_BLOCK,
+                                  n: int | None = None, time: float | None = None) -> int:
+        """render_backward_scene with the depth and feature planes
+        (gsr_render_backward_scene_aux, include/gsr.h): render_backward_aux into ELEVEN record
+        planes (the ten of render_backward_scene, then z), project_backward_aux from them.
+        scratch_ptr: 11*n float32, or None.  feat_grad_ptr: nfeat planes of n, ACCUMULATED, the
+        feature gradients (they have no scene array).  Same returns as render()."""
+        outs = [_dev_ptr(p) for p in (position_ptr, opacity_ptr, scale_ptr, rot_ptr, sh_ptr, temporal_ptr)]
+        fg = _dev_ptr(feat_grad_ptr)
+        up = self._aux_upstream("render_backward_scene_aux", grad_image_ptr, grad_alpha_ptr, grad_depth_ptr,
+                                grad_feat_ptr, features_ptr, nfeat, fg)
+        if not any(outs):
+            raise ValueError("render_backward_scene_aux: no output requested")
+        ptr = scene.ptr if isinstance(scene, Scene) else int(scene)
+        n = scene.n if n is None else n
+        if isinstance(scene, Scene) and layout == LAYOUT_SCENE_BLOCK:
+            layout = scene.layout
+        if time is not None:
+            self.set_time(time)
+        t = tiling or TilingInformation(1, 1, H, W)
+        sg = SceneGrads(*[p or None for p in outs])
+        rc = lib().gsr_render_backward_scene_aux(self.ctx, ptr, layout, n, byref(cam), W, H, t.num_tile_x,
+                                                 t.num_tile_y, t.width_stride, t.height_stride, k, byref(up),
+                                                 fg or None, _dev_ptr(scratch_ptr) or None, byref(sg), stream or None)
+        if rc not in (_native.GSR_OK, _native.GSR_E_OVERFLOW):
+            raise GsrError(rc, "gsr_render_backward_scene_aux")
         return rc
 
     def set_frames_in_flight(self, frames: int):

@@ -140,6 +140,45 @@ class RecordGrads(ctypes.Structure):
     ]
 
 
+class AuxUpstream(ctypes.Structure):
+    """``gsr_aux_upstream`` (include/gsr.h): the upstream gradients of gsr_render_backward_aux and
+    the per-Gaussian feature values its feature channels composite."""
+
+    _fields_ = [
+        ("d_grad_image", c_void_p),
+        ("d_grad_alpha", c_void_p),
+        ("d_grad_depth", c_void_p),
+        ("d_grad_feat", c_void_p),
+        ("d_features", c_void_p),
+        ("nfeat", c_int),
+    ]
+
+
+class RecordGradsAuxOut(ctypes.Structure):
+    """``gsr_record_grads_aux_out`` (include/gsr.h): the outputs of gsr_render_backward_aux."""
+
+    _fields_ = [
+        ("d_color", c_void_p),
+        ("d_opacity", c_void_p),
+        ("d_conic", c_void_p),
+        ("d_center", c_void_p),
+        ("d_z", c_void_p),
+        ("d_feat", c_void_p),
+    ]
+
+
+class RecordGradsAux(ctypes.Structure):
+    """``gsr_record_grads_aux`` (include/gsr.h): the inputs of gsr_project_backward_aux."""
+
+    _fields_ = [
+        ("d_color", c_void_p),
+        ("d_opacity", c_void_p),
+        ("d_conic", c_void_p),
+        ("d_center", c_void_p),
+        ("d_z", c_void_p),
+    ]
+
+
 class SceneGrads(ctypes.Structure):
     """``gsr_scene_grads`` (include/gsr.h): the outputs of gsr_project_backward and
     gsr_render_backward_scene."""
@@ -254,6 +293,14 @@ SIGNATURES = [
     ("gsr_render_backward_scene", c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(Camera), c_int, c_int, c_int,
                                           c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
                                           POINTER(SceneGrads), c_void_p]),
+    ("gsr_render_backward_aux", c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(Camera), c_int, c_int, c_int,
+                                        c_int, c_int, c_int, c_float, POINTER(AuxUpstream),
+                                        POINTER(RecordGradsAuxOut), c_void_p]),
+    ("gsr_project_backward_aux", c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(Camera), c_int, c_int, c_float,
+                                         POINTER(RecordGradsAux), POINTER(SceneGrads), c_void_p]),
+    ("gsr_render_backward_scene_aux", c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(Camera), c_int, c_int,
+                                              c_int, c_int, c_int, c_int, c_float, POINTER(AuxUpstream), c_void_p,
+                                              c_void_p, POINTER(SceneGrads), c_void_p]),
     ("gsr_render_path", c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(Camera), c_void_p, c_int, c_int,
                                 c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     ("gsr_render_path_ex", c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(Camera), c_void_p, c_int, c_int,

@@ -1,6 +1,7 @@
 // gsr_blend_derived.hip — the passes derived from the exact blend (gfx950, CDNA4): k_blend_aux
-// (gsr_render_aux), k_blend_contrib (gsr_render_contrib) and k_blend_backward
-// (gsr_render_backward), with the per-Gaussian kernels that feed them.  Each walks a block's
+// (gsr_render_aux), k_blend_contrib (gsr_render_contrib), k_blend_backward
+// (gsr_render_backward) and k_blend_backward_aux (gsr_render_backward_aux), with the
+// per-Gaussian kernels that feed them.  Each walks a block's
 // list with the functions of gsr_blend_device.h — k_blend_w's schedule, cull and exact
 // one-splat step (gsr_blend.hip) — and owns only its LDS slot layout, what it accumulates per
 // take and its epilogue (k_blend_aux also its copy of the record load and prefetch).  Compiled like gsr_blend.hip: -ffp-contract=off, gsr_detmath.h.
@@ -588,6 +589,253 @@ __global__ __launch_bounds__(64, 8) void k_blend_backward(const uint32_t* __rest
     }
 }
 
+// k_blend_backward_aux's upstream gradients (W*H planes, nullable each; g_feat: nfeat planes),
+// the per-Gaussian values its depth and feature channels composite (as AuxIO), the planar
+// per-Gaussian gradient arrays it adds to (nullable each) and the frame's overflow word.
+struct BackwardAuxIO {
+    const float* g_image;
+    const float* g_alpha;
+    const float* g_depth;
+    const float* g_feat;
+    const float* features;   // nfeat arrays of n floats (NF = 4, GEO)
+    const float4* pack;      // k_aux_pack's output (NF = 8, GEO)
+    const float* z;          // k_aux_depth's output (DEPTH, GEO)
+    float* color;
+    float* opacity;
+    float* conic;
+    float* center;
+    float* dz;               // n floats
+    float* feat;             // nfeat planes of n floats
+    int64_t n;
+    int nfeat;
+    const uint32_t* overflow;
+};
+
+// The backward pass of the exact blend with the depth and feature channels
+// (gsr_render_backward_aux): gradients of L = sum over pixels of g_rgb . image + g_A alpha +
+// g_D depth + sum_f g_f feat_f.  k_blend_backward's schedule, decisions, two forward sweeps
+// and in-wave reduction, with
+//   u_j = g_rgb . colour_j + g_A + g_D z_j + sum_f g_f phi_f,j
+// in place of its u, and two more linear outputs per taken splat: dz += g_D alpha T and
+// feat[f] += g_f alpha T.  z and phi are gathered by Gaussian index by the hit lane, as
+// k_blend_aux does it (up to four features from the planar arrays, more from k_aux_pack's
+// interleaved copy), so they are the forward's floats.  Only u reads them: without GEO the
+// slots' dwords [10] and [12 ..] hold nothing before the sums, and z, features and pack are
+// not needed at all.
+//
+// Survivor k's slot (12 + NF dwords, read with wave-uniform addresses) is k_blend_aux's:
+//   [0] cx [1] cy [2] a [3] b | [4] c [5] e [6] opacity [7] r | [8] g [9] b [10] -Z [11] unused
+//   | [12 ..] features
+// The sums go over the slot once the loop has read it: colour 3, then (GEO) opacity 1, conic
+// 3, centre 2, then (DEPTH) z 1 from dword 0 on — at most 10 — and the feature sums in their
+// own dwords from 12 on, reduced four at a time so that at most ten values are live at once.
+//
+// NF: the feature channels in u and in the sums, padded to 0 / 4 / 8.  DEPTH: g_D given (z in
+// u, the z sum).  GEO: any of opacity, conic, centre wanted; without it nothing needs
+// dL/dalpha, hence neither P nor G, and the kernel makes ONE sweep (every remaining output is
+// linear in alpha T).  Which planes of a group are written is decided at the atomic.
+// NF = 8 asks for six waves per SIMD like k_blend_aux<8> (5 KiB of LDS per wave), and so does
+// NF = 4 with GEO, which at eight (64 VGPRs) spills 20 bytes.
+template <int NF, bool DEPTH, bool GEO>
+__global__ __launch_bounds__(64, (NF > 4 || (NF == 4 && GEO)) ? 6 : 8) void k_blend_backward_aux(
+    const uint32_t* __restrict__ idx, const uint2* __restrict__ ranges, const uint4* __restrict__ rec, int tiles_x,
+    int tiles_y, int W, int H, int cover_w, int cover_h, int bands, BackwardAuxIO io) {
+    constexpr int oC = 0, oO = 3, oK = 4, oX = 7, oZ = GEO ? 9 : 3;
+    constexpr int NV = oZ + (DEPTH ? 1 : 0), NX = (NV + 3) / 4;
+    constexpr int kSlot = 12 + NF, oF = 12;
+    constexpr int kNF = NF ? NF : 1;
+    __shared__ float4 sP[64 * (kSlot / 4)];
+    if (*io.overflow) return;   // uniform: an incomplete frame adds nothing
+    BlockSetup bs;
+    if (!block_setup(bs, ranges, tiles_x, tiles_y, cover_w, cover_h, bands)) return;
+    const uint32_t beg = bs.beg, end = bs.end;
+    const int lane = bs.lane, px = bs.px, py = bs.py;
+    const bool inside = bs.inside;
+    const float fpx = bs.fpx, fpy = bs.fpy;
+    const float4* wP4 = sP;
+    float* wF = reinterpret_cast<float*>(sP);
+
+    // the pixel's upstream gradient; pixels outside the covered area composite nothing
+    float g_r = 0.0f, g_g = 0.0f, g_b = 0.0f, g_a = 0.0f, g_d = 0.0f, g_f[kNF];
+#pragma unroll
+    for (int f = 0; f < kNF; f++) g_f[f] = 0.0f;
+    if (inside && px < W && py < H) {
+        const size_t o = (size_t)py * (size_t)W + (size_t)px;
+        const size_t hw = (size_t)W * (size_t)H;
+        if (io.g_image) {
+            g_r = io.g_image[o];
+            g_g = io.g_image[hw + o];
+            g_b = io.g_image[2 * hw + o];
+        }
+        if (io.g_alpha) g_a = io.g_alpha[o];
+        if (DEPTH) g_d = io.g_depth[o];
+#pragma unroll
+        for (int f = 0; f < NF; f++)   // padding channels: no upstream
+            if (f < io.nfeat) g_f[f] = io.g_feat[(size_t)f * hw + o];
+    }
+
+    float G = 0.0f;
+#pragma nounroll
+    for (int sweep = GEO ? 0 : 1; sweep < 2; ++sweep) {
+        // pixels outside the covered area start saturated and composite nothing (blend_block)
+        float T = inside ? 1.0f : 0.0f;
+        float P = 0.0f;
+        RecordBatch B;
+        batch_first(B, idx, rec, beg, end, lane);
+        bool alive = __ballot(!(T < 1e-3f)) != 0ull;
+        for (uint32_t base = beg; base < end && alive; base += 64) {
+            const uint32_t cnt = min(64u, end - base);
+            // ---- cull (lane = record) ----
+            BlockCull cl;
+            const bool hit = block_cull(cl, B.ra, B.rc, B.rd, bs.bx, bs.by, lane, cnt, __ballot(!(T < 1e-3f)));
+            const uint32_t dsc = cl.dsc;
+            // ---- survivors, compacted in list order; each gathers its -Z and features ----
+            const uint64_t m = __ballot(hit);
+            const uint32_t k_l = ballot_rank(m);
+            const uint32_t gidx = B.cidx;   // this batch's Gaussian index of record `lane`
+            float zv = 0.0f, fv[kNF];
+#pragma unroll
+            for (int f = 0; f < kNF; f++) fv[f] = 0.0f;
+            if (hit) {
+                // (only u reads -Z and the features: without GEO nothing gathers them)
+                if (DEPTH && GEO) zv = io.z[gidx];
+                if (GEO && NF == 8) {
+                    const float4 p0 = io.pack[2 * (int64_t)gidx], p1 = io.pack[2 * (int64_t)gidx + 1];
+                    fv[0] = p0.x; fv[1 % kNF] = p0.y; fv[2 % kNF] = p0.z; fv[3 % kNF] = p0.w;
+                    fv[4 % kNF] = p1.x; fv[5 % kNF] = p1.y; fv[6 % kNF] = p1.z; fv[7 % kNF] = p1.w;
+                } else if (GEO) {
+#pragma unroll
+                    for (int f = 0; f < NF; f++)   // padding channels repeat the last array (their g_f is 0)
+                        fv[f] = io.features[(int64_t)min(f, io.nfeat - 1) * io.n + (int64_t)gidx];
+                }
+                float4* S4 = sP + k_l * (kSlot / 4);
+                S4[0] = make_float4(__uint_as_float(B.rc.x), __uint_as_float(B.rc.y), __uint_as_float(B.ra.x),
+                                    __uint_as_float(B.ra.y));
+                S4[1] = make_float4(__uint_as_float(B.ra.z), __uint_as_float(B.ra.w), __uint_as_float(B.rb.x),
+                                    __uint_as_float(B.rb.y));
+            }
+            const float col_g = __uint_as_float(B.rb.z), col_b = __uint_as_float(B.rb.w);
+            batch_prefetch(B, idx, rec, base, end, lane);
+            if (hit) {
+                // (the gathered values last: their loads were issued ahead of the prefetch)
+                float4* S4 = sP + k_l * (kSlot / 4);
+                S4[2] = make_float4(col_g, col_b, zv, 0.0f);
+                if (GEO && NF >= 4) S4[3] = make_float4(fv[0], fv[1 % kNF], fv[2 % kNF], fv[3 % kNF]);
+                if (GEO && NF >= 8) S4[4] = make_float4(fv[4 % kNF], fv[5 % kNF], fv[6 % kNF], fv[7 % kNF]);
+            }
+            // ---- the exact one-splat step over the survivors (render.cu:329-340) ----
+            uint64_t taken = 0;   // survivors whose slot holds sums
+            uint64_t mm = m;
+            for (uint32_t k = 0; mm && alive; ++k) {
+                const int s = __builtin_ctzll(mm);
+                mm &= mm - 1;
+                const uint64_t box = box_mask((uint32_t)__builtin_amdgcn_readlane((int)dsc, s));
+                const float4 q0 = wP4[k * (kSlot / 4) + 0], q1 = wP4[k * (kSlot / 4) + 1];
+                const float4 q2 = wP4[k * (kSlot / 4) + 2];
+                SplatStep st;
+                const bool take = splat_step(st, fpx, fpy, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, box, T);
+                const float dx = st.dx, dy = st.dy, ee = st.ee, oe = st.oe, alpha = st.alpha;
+                if (__ballot(take)) {   // uniform
+                    const float w = alpha * T;
+                    float u = 0.0f;
+                    if (GEO) {
+                        u = __builtin_fmaf(g_r, q1.w, __builtin_fmaf(g_g, q2.x, __builtin_fmaf(g_b, q2.y, g_a)));
+                        if (DEPTH) u = __builtin_fmaf(g_d, q2.z, u);
+                        if (NF >= 4) {
+                            const float4 q3 = wP4[k * (kSlot / 4) + 3];
+                            u = __builtin_fmaf(g_f[0], q3.x, u);
+                            u = __builtin_fmaf(g_f[1 % kNF], q3.y, u);
+                            u = __builtin_fmaf(g_f[2 % kNF], q3.z, u);
+                            u = __builtin_fmaf(g_f[3 % kNF], q3.w, u);
+                        }
+                        if (NF >= 8) {
+                            const float4 q4 = wP4[k * (kSlot / 4) + 4];
+                            u = __builtin_fmaf(g_f[4 % kNF], q4.x, u);
+                            u = __builtin_fmaf(g_f[5 % kNF], q4.y, u);
+                            u = __builtin_fmaf(g_f[6 % kNF], q4.z, u);
+                            u = __builtin_fmaf(g_f[7 % kNF], q4.w, u);
+                        }
+                        const float Pn = __builtin_fmaf(u, w, P);
+                        P = take ? Pn : P;
+                    }
+                    if (sweep) {
+                        float v[NV];
+                        const float wt = take ? w : 0.0f;
+                        v[oC] = g_r * wt;
+                        v[oC + 1] = g_g * wt;
+                        v[oC + 2] = g_b * wt;
+                        if (GEO) {
+                            // (1 - alpha >= 0.01; the clamped alpha passes nothing on)
+                            float da = T * u - (G - P) * __builtin_amdgcn_rcpf(1.0f - alpha);
+                            da = (take & !(oe > 0.99f)) ? da : 0.0f;
+                            v[oO % NV] = da * ee;
+                            const float dmd = -0.5f * oe * da;
+                            v[oK % NV] = dmd * dx * dx;
+                            v[(oK + 1) % NV] = dmd * dx * dy;
+                            v[(oK + 2) % NV] = dmd * dy * dy;
+                            const float bc = q0.w + q1.x;
+                            v[oX % NV] = -dmd * (2.0f * q0.z * dx + bc * dy);
+                            v[(oX + 1) % NV] = -dmd * (bc * dx + 2.0f * q1.y * dy);
+                        }
+                        if (DEPTH) v[oZ % NV] = g_d * wt;
+                        float x[NX];
+                        wave_sum_packed<NV>(v, x);
+                        if ((lane & 15) == 0) {
+#pragma unroll
+                            for (int i = 0; i < NX; i++) {
+                                const int vi = backward_slot<NV>(i, lane >> 4);
+                                if (vi >= 0) wF[k * kSlot + vi] = x[i];
+                            }
+                        }
+#pragma unroll
+                        for (int f0 = 0; f0 < NF; f0 += 4) {   // row r of the wave ends up with feature f0 + slot(0, r)
+                            const float vf[4] = {g_f[f0 % kNF] * wt, g_f[(f0 + 1) % kNF] * wt, g_f[(f0 + 2) % kNF] * wt,
+                                                 g_f[(f0 + 3) % kNF] * wt};
+                            float xf[1];
+                            wave_sum_packed<4>(vf, xf);
+                            if ((lane & 15) == 0) wF[k * kSlot + oF + f0 + backward_slot<4>(0, lane >> 4)] = xf[0];
+                        }
+                        taken |= 1ull << k;
+                    }
+                    const float Tn = T * (1.0f - alpha);
+                    T = take ? Tn : T;
+                    alive = __ballot(!(T < 1e-3f)) != 0ull;
+                }
+            }
+            // ---- one atomic per component per survivor that some pixel composited (lane = survivor) ----
+            if (sweep && hit && ((taken >> k_l) & 1ull)) {
+                const float* r = wF + k_l * kSlot;
+                const int64_t n = io.n;
+                if (io.color) {
+                    atomicAdd(io.color + gidx, r[oC]);
+                    atomicAdd(io.color + n + gidx, r[oC + 1]);
+                    atomicAdd(io.color + 2 * n + gidx, r[oC + 2]);
+                }
+                if (GEO) {
+                    if (io.opacity) atomicAdd(io.opacity + gidx, r[oO]);
+                    if (io.conic) {
+                        atomicAdd(io.conic + gidx, r[oK]);
+                        atomicAdd(io.conic + n + gidx, r[oK + 1]);
+                        atomicAdd(io.conic + 2 * n + gidx, r[oK + 1]);
+                        atomicAdd(io.conic + 3 * n + gidx, r[oK + 2]);
+                    }
+                    if (io.center) {
+                        atomicAdd(io.center + gidx, r[oX]);
+                        atomicAdd(io.center + n + gidx, r[oX + 1]);
+                    }
+                }
+                if (DEPTH && io.dz) atomicAdd(io.dz + gidx, r[oZ]);
+                if (NF > 0 && io.feat) {
+#pragma unroll
+                    for (int f = 0; f < NF; f++)
+                        if (f < io.nfeat) atomicAdd(io.feat + (int64_t)f * n + gidx, r[oF + f]);
+                }
+            }
+        }
+        G = P;
+    }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------ launchers
@@ -664,6 +912,57 @@ hipError_t launch_blend_backward(const uint32_t* idx, const uint2* ranges, const
         hipLaunchKernelGGL((k_blend_backward<decltype(w)::value>), dim3(ng), dim3(64), 0, s, idx, ranges, rec,
                            fr.tiles_x, fr.tiles_y, fr.W, fr.H, fr.cover_w, fr.cover_h, bands, io);
     });
+    return hipGetLastError();
+}
+
+hipError_t launch_blend_backward_aux(const uint32_t* idx, const uint2* ranges, const uint4* rec, const Frame& fr,
+                                     const float* g_image, const float* g_alpha, const float* g_depth,
+                                     const float* g_feat, const float* features, int nfeat, const float* z,
+                                     float4* pack, float* color, float* opacity, float* conic, float* center,
+                                     float* dz, float* feat, int64_t n, const uint32_t* overflow, int band_tiles,
+                                     hipStream_t s) {
+    if (nfeat < 0 || nfeat > 8 || (nfeat > 0 && !features) || (nfeat == 0 && (g_feat || feat)) ||
+        (!g_image && !g_alpha && !g_depth && !g_feat) ||
+        (!color && !opacity && !conic && !center && !dz && !feat) || !overflow)
+        return hipErrorInvalidValue;
+    // an output whose upstream is missing is identically zero: not touched
+    if (!g_image) color = nullptr;
+    if (!g_depth) dz = nullptr;
+    if (!g_feat) feat = nullptr;
+    const bool geo = opacity || conic || center;
+    if (!geo && !color && !dz && !feat) return hipSuccess;
+    // what the kernel has to carry: the depth and feature channels only where they reach an output
+    const bool depth = g_depth && (geo || dz);
+    const int nf = (g_feat && (geo || feat)) ? nfeat : 0;
+    if (!depth && nf == 0)   // nothing beyond k_blend_backward's function
+        return launch_blend_backward(idx, ranges, rec, fr, g_image, g_alpha, color, opacity, conic, center, n, overflow,
+                                     band_tiles, s);
+    // (-Z and the feature values enter through u alone, which only the geometry outputs need)
+    if (geo && ((depth && !z) || (nf > 4 && !pack))) return hipErrorInvalidValue;
+    const int nt = fr.tiles_x * fr.tiles_y;
+    if (nt <= 0 || n <= 0) return hipSuccess;
+    int bands, ng;
+    blend_grid(nt, band_tiles, bands, ng);
+    if (geo && nf > 4) hipLaunchKernelGGL(k_aux_pack, dim3(grid_for(n, 256)), dim3(256), 0, s, features, n, nf, pack);
+    const BackwardAuxIO io{g_image, g_alpha, depth ? g_depth : nullptr, nf ? g_feat : nullptr, features, pack,
+                           (depth && geo) ? z : nullptr, color, opacity, conic, center, dz, nf ? feat : nullptr, n, nf,
+                           overflow};
+    // features padded to 0 / 4 / 8 channels
+    auto go = [&](auto nfc) {
+        constexpr int NF = decltype(nfc)::value;
+        with_bool(depth, [&](auto d) {
+            with_bool(geo, [&](auto g) {
+                // (NF = 0 without DEPTH went to launch_blend_backward above: not instantiated)
+                if constexpr (NF > 0 || decltype(d)::value)
+                    hipLaunchKernelGGL((k_blend_backward_aux<NF, decltype(d)::value, decltype(g)::value>), dim3(ng),
+                                       dim3(64), 0, s, idx, ranges, rec, fr.tiles_x, fr.tiles_y, fr.W, fr.H,
+                                       fr.cover_w, fr.cover_h, bands, io);
+            });
+        });
+    };
+    if (nf == 0) go(std::integral_constant<int, 0>{});
+    else if (nf <= 4) go(std::integral_constant<int, 4>{});
+    else go(std::integral_constant<int, 8>{});
     return hipGetLastError();
 }
 

@@ -160,7 +160,7 @@ struct gsr_context {
     int split_state_hold = -1;       // >= 0: the sorted frame is an aux frame (gsr_render_aux), and
                                      // GSR_TUNE_DEPTH_SPLIT_STATE reads this, the state of the frame before it
     DevBuf<float> aux_z;             // gsr_render_aux: -Z per Gaussian (the depth channel's values)
-    DevBuf<float> rec_grads;         // gsr_render_backward_scene without a caller's scratch: ten planes of n floats
+    DevBuf<float> rec_grads;         // gsr_render_backward_scene without a caller's scratch: ten planes of n floats (_aux: eleven)
     DevBuf<float4> aux_pack;         // gsr_render_aux, nfeat > 4: the features interleaved per Gaussian
     int fail_frame = 0;              // GSR_TUNE_FAIL_FRAME: gsr_render_path fails this frame (> 0) once
     uint32_t* fstatus = nullptr;     // the current frame's validity word (gsr_render_path_status; device,

@@ -261,14 +261,30 @@ hipError_t launch_blend_backward(const uint32_t* idx, const uint2* ranges, const
                                  const float* g_image, const float* g_alpha, float* color, float* opacity,
                                  float* conic, float* center, int64_t n, const uint32_t* overflow, int band_tiles,
                                  hipStream_t s);
+// Backward pass of the exact blend with the depth and feature channels
+// (gsr_render_backward_aux; k_blend_backward_aux): launch_blend_backward's with g_depth (W*H)
+// and g_feat (nfeat planes of W*H) as further upstream gradients, the channels' per-Gaussian
+// values (features: nfeat arrays of n; z: launch_aux_depth's output, needed with g_depth;
+// pack: 2 n float4 of workspace for nfeat > 4; z and pack only when opacity, conic or center
+// is wanted: nothing else reads the values) and the outputs dz (n) and feat (nfeat planes
+// of n), ACCUMULATED like the others.  An output without its upstream (color without g_image,
+// dz without g_depth, feat without g_feat) is not touched.  Where neither channel reaches an
+// output wanted, this is launch_blend_backward itself.
+hipError_t launch_blend_backward_aux(const uint32_t* idx, const uint2* ranges, const uint4* rec, const Frame& fr,
+                                     const float* g_image, const float* g_alpha, const float* g_depth,
+                                     const float* g_feat, const float* features, int nfeat, const float* z,
+                                     float4* pack, float* color, float* opacity, float* conic, float* center,
+                                     float* dz, float* feat, int64_t n, const uint32_t* overflow, int band_tiles,
+                                     hipStream_t s);
 // Backward pass of the projection (gsr_project_backward; k_project_backward, gsr_project.hip):
 // the record gradients `in` (planes of n floats, NULL = zeros) carried on to the scene-array
 // gradients `out` (ACCUMULATED, one thread per Gaussian, no atomics).  arrays / stride /
 // four_d / sh3 / t as given to launch_preprocess; of fr it reads the camera, W, H and znear.
-// Launch geometry from n alone; n == 0 launches nothing.
+// Launch geometry from n alone; n == 0 launches nothing.  in_z (gsr_project_backward_aux, n
+// floats or NULL): dL/d(-Z), an eleventh upstream entry; NULL runs the ten-entry kernel.
 hipError_t launch_project_backward(const float* arrays, int64_t stride, int64_t n, const Frame& fr, bool four_d,
                                    bool sh3, float t, const gsr_record_grads& in, const gsr_scene_grads& out,
-                                   hipStream_t s);
+                                   hipStream_t s, const float* in_z = nullptr);
 // Stable partition of the preprocess items: visible first, culled last (both in
 // index order), visible count into *n_live; culled tail to out only, with dead
 // rects in srect (gsr_kernels.hip "live partition").  counts: groups words.

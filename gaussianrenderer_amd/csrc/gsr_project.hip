@@ -91,16 +91,19 @@ struct PlanesWg {
 };
 
 // One Gaussian per lane, 256 per workgroup.  T4D: a 49-array block at time tnow; SH3: a
-// 59-array block (bands 0..3, clamped at 0 only).
-template <bool T4D, bool SH3>
+// 59-array block (bands 0..3, clamped at 0 only).  DZ (gsr_project_backward_aux): in_z holds
+// an eleventh upstream entry, dL/d(-Z); without it the kernel is the ten-entry one, operation
+// for operation (in_z, last, is not read).
+template <bool T4D, bool SH3, bool DZ>
 __global__ __launch_bounds__(256) void k_project_backward(const float* __restrict__ arr, int64_t stride, int64_t n,
                                                           Frame fr, float tnow, const gsr_record_grads in,
-                                                          const gsr_scene_grads out) {
+                                                          const gsr_scene_grads out, const float* __restrict__ in_z) {
     const int64_t i0 = (int64_t)blockIdx.x * 256;
     if (i0 + threadIdx.x >= n) return;
     const PlanesWg G{n, i0, threadIdx.x};
 
-    // ---- upstream: the ten record gradients; all zero = the frame never composited it ----
+    // ---- upstream: the ten record gradients (DZ: and dL/d(-Z)); all zero = the frame never
+    // composited it ----
     float g_col[3], g_con[4], g_cen[2];
 #pragma unroll
     for (int c = 0; c < 3; c++) g_col[c] = G.in(in.d_color, c);
@@ -109,8 +112,10 @@ __global__ __launch_bounds__(256) void k_project_backward(const float* __restric
     for (int c = 0; c < 4; c++) g_con[c] = G.in(in.d_conic, c);
 #pragma unroll
     for (int c = 0; c < 2; c++) g_cen[c] = G.in(in.d_center, c);
+    const float g_z = DZ ? G.in(in_z, 0) : 0.0f;
     if (g_col[0] == 0.0f && g_col[1] == 0.0f && g_col[2] == 0.0f && g_op == 0.0f && g_con[0] == 0.0f &&
-        g_con[1] == 0.0f && g_con[2] == 0.0f && g_con[3] == 0.0f && g_cen[0] == 0.0f && g_cen[1] == 0.0f)
+        g_con[1] == 0.0f && g_con[2] == 0.0f && g_con[3] == 0.0f && g_cen[0] == 0.0f && g_cen[1] == 0.0f &&
+        (!DZ || g_z == 0.0f))
         return;
 
     // ---- forward, as preprocess_camera: view, clip, 2D covariance, the three tests ----
@@ -197,6 +202,10 @@ __global__ __launch_bounds__(256) void k_project_backward(const float* __restric
 #pragma unroll
     for (int j = 0; j < 3; j++)
         d_pos[j] = fr.V[j] * d_view[0] + fr.V[4 + j] * d_view[1] + fr.V[8 + j] * d_view[2] + fr.V[12 + j] * d_view[3];
+    if (DZ) {   // Z = (V [p, 1])_z: dL/dp += -V[2][.] dL/d(-Z)
+#pragma unroll
+        for (int j = 0; j < 3; j++) d_pos[j] += -fr.V[8 + j] * g_z;
+    }
 
     // ---- covariance: dL/dSigma_c = J^T dT J, dL/dSigma = Rc^T (.) Rc, N = R S, Sigma = N N^T,
     // dL/dN = (G + G^T) N; then the scales, the rotation matrix and the quaternion ----
@@ -336,15 +345,18 @@ __global__ __launch_bounds__(256) void k_project_backward(const float* __restric
 
 hipError_t launch_project_backward(const float* arrays, int64_t stride, int64_t n, const Frame& fr, bool four_d,
                                    bool sh3, float t, const gsr_record_grads& in, const gsr_scene_grads& out,
-                                   hipStream_t s) {
+                                   hipStream_t s, const float* in_z) {
     if (n <= 0) return hipSuccess;
     const int grid = grid_for(n, 256);
-    if (four_d)
-        k_project_backward<true, false><<<grid, 256, 0, s>>>(arrays, stride, n, fr, t, in, out);
-    else if (sh3)
-        k_project_backward<false, true><<<grid, 256, 0, s>>>(arrays, stride, n, fr, t, in, out);
-    else
-        k_project_backward<false, false><<<grid, 256, 0, s>>>(arrays, stride, n, fr, t, in, out);
+    with_bool(in_z != nullptr, [&](auto dz) {
+        constexpr bool DZ = decltype(dz)::value;
+        if (four_d)
+            k_project_backward<true, false, DZ><<<grid, 256, 0, s>>>(arrays, stride, n, fr, t, in, out, in_z);
+        else if (sh3)
+            k_project_backward<false, true, DZ><<<grid, 256, 0, s>>>(arrays, stride, n, fr, t, in, out, in_z);
+        else
+            k_project_backward<false, false, DZ><<<grid, 256, 0, s>>>(arrays, stride, n, fr, t, in, out, in_z);
+    });
     return hipGetLastError();
 }
 

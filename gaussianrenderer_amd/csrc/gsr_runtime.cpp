@@ -1152,10 +1152,11 @@ int check_scene_grads(const char* who, const gsr_scene_grads* out, int layout) {
 }
 
 int project_backward_launch(const gsr_context* c, const void* scene, int layout, int64_t n, const Frame& fr,
-                            const gsr_record_grads& in, const gsr_scene_grads& out, hipStream_t s) {
+                            const gsr_record_grads& in, const gsr_scene_grads& out, hipStream_t s,
+                            const float* in_z = nullptr) {
     if (n == 0) return GSR_OK;
     HIP_TRY(gsr::launch_project_backward(scene_arrays(scene), scene_stride(n), n, fr, layout == GSR_LAYOUT_SCENE_BLOCK_4D,
-                                         layout == GSR_LAYOUT_SCENE_BLOCK_SH3, c->time, in, out, s));
+                                         layout == GSR_LAYOUT_SCENE_BLOCK_SH3, c->time, in, out, s, in_z));
     return GSR_OK;
 }
 
@@ -1203,6 +1204,123 @@ extern "C" int gsr_render_backward_scene(gsr_context* c, const void* scene, int 
     if (rc != GSR_OK && rc != GSR_E_OVERFLOW) return rc;
     const gsr_record_grads in{planes, planes + 3 * n, planes + 4 * n, planes + 8 * n};
     if (int r2 = project_backward_launch(c, scene, layout, n, c->fr, in, *out, c->stream)) return r2;
+    return rc;
+}
+
+// ------------------------------------------------------------------ backward with the depth and feature planes
+
+namespace {
+
+// What gsr_render_backward_aux and gsr_render_backward_scene_aux refuse in their upstream.
+int check_aux_upstream(const char* who, const gsr_aux_upstream* up, const float* d_feat) {
+    if (!up) return set_err(GSR_E_ARG, "%s: null upstream", who);
+    if (up->nfeat < 0 || up->nfeat > GSR_AUX_MAX_FEATURES)
+        return set_err(GSR_E_ARG, "%s: nfeat %d out of range [0, %d]", who, up->nfeat, GSR_AUX_MAX_FEATURES);
+    if (up->nfeat > 0 && !up->d_features) return set_err(GSR_E_ARG, "%s: nfeat %d needs d_features", who, up->nfeat);
+    if (up->nfeat == 0 && (up->d_grad_feat || d_feat))
+        return set_err(GSR_E_ARG, "%s: feature gradients given with nfeat 0", who);
+    if (!up->d_grad_image && !up->d_grad_alpha && !up->d_grad_depth && !up->d_grad_feat)
+        return set_err(GSR_E_ARG, "%s: no upstream gradient", who);
+    return GSR_OK;
+}
+
+// The sorted frame's backward pass with the depth and feature channels: blend_backward_locked
+// with k_blend_backward_aux, behind blend_aux_locked's -Z kernel and workspaces where a
+// channel reaches an output.  Without either channel it is blend_backward_locked.
+int blend_backward_aux_locked(gsr_context* c, const gsr_aux_upstream& up, const gsr_record_grads_aux_out& o) {
+    const bool geo = o.d_opacity || o.d_conic || o.d_center;
+    if (!up.d_grad_depth && !up.d_grad_feat && !o.d_z && !o.d_feat) {
+        // (d_color without d_grad_image is identically zero: not touched here either)
+        float* color = up.d_grad_image ? o.d_color : nullptr;
+        if (!color && !geo) {
+            mark(c, GSR_STAGE_BLEND);
+            return frame_done(c);
+        }
+        const gsr_backward_targets bw{up.d_grad_image, up.d_grad_alpha, color, o.d_opacity, o.d_conic, o.d_center};
+        return blend_backward_locked(c, bw);
+    }
+    // -Z and the feature values enter through u alone, which only the geometry outputs need
+    const bool with_z = up.d_grad_depth && geo && c->n > 0;
+    const bool with_pack = up.nfeat > 4 && up.d_grad_feat && geo && c->n > 0;
+    if (with_z) {
+        if (int rc = c->aux_z.reserve(per_gaussian(c->n))) return rc;
+    }
+    if (with_pack) {
+        if (int rc = c->aux_pack.reserve(2 * per_gaussian(c->n))) return rc;
+    }
+    mark(c, GSR_STAGE_BLEND);   // the stage holds the -Z and feature-pack kernels too
+    if (with_z)
+        HIP_TRY(gsr::launch_aux_depth(c->pre_arrays, c->pre_stride, c->n, c->fr,
+                                      c->pre_layout == GSR_LAYOUT_SCENE_BLOCK_4D, c->time, c->aux_z, c->stream));
+    HIP_TRY(gsr::launch_blend_backward_aux(pair_vals(c, c->pair_buf), c->ranges, c->rec, c->fr, up.d_grad_image,
+                                           up.d_grad_alpha, up.d_grad_depth, up.d_grad_feat, up.d_features, up.nfeat,
+                                           c->aux_z, c->aux_pack, o.d_color, o.d_opacity, o.d_conic, o.d_center,
+                                           o.d_z, o.d_feat, c->n, &c->stats[0].overflow, c->set.blend_band_tiles,
+                                           c->stream));
+    return frame_done(c);
+}
+
+}  // namespace
+
+extern "C" int gsr_render_backward_aux(gsr_context* c, const void* scene, int layout, int64_t n,
+                                       const gsr_camera* cam, int W, int H, int nx, int ny, int ws, int hs, float k,
+                                       const gsr_aux_upstream* up, const gsr_record_grads_aux_out* out,
+                                       void* stream) {
+    if (!c) return set_err(GSR_E_ARG, "null context");
+    if (!out) return set_err(GSR_E_ARG, "gsr_render_backward_aux: null outputs");
+    if (int rc = check_aux_upstream("gsr_render_backward_aux", up, out->d_feat)) return rc;
+    if (!out->d_color && !out->d_opacity && !out->d_conic && !out->d_center && !out->d_z && !out->d_feat)
+        return set_err(GSR_E_ARG, "gsr_render_backward_aux: no output");
+    std::lock_guard<std::mutex> lk(c->mu);
+    return aux_frame_locked(c, scene, layout, n, cam, W, H, nx, ny, ws, hs, k, stream,
+                            [&] { return blend_backward_aux_locked(c, *up, *out); });
+}
+
+extern "C" int gsr_project_backward_aux(gsr_context* c, const void* scene, int layout, int64_t n,
+                                        const gsr_camera* cam, int W, int H, float k, const gsr_record_grads_aux* in,
+                                        const gsr_scene_grads* out, void* stream) {
+    if (!c) return set_err(GSR_E_ARG, "null context");
+    if (!in) return set_err(GSR_E_ARG, "gsr_project_backward_aux: null inputs");
+    if (!in->d_color && !in->d_opacity && !in->d_conic && !in->d_center && !in->d_z)
+        return set_err(GSR_E_ARG, "gsr_project_backward_aux: no upstream gradient");
+    if (int rc = check_scene_grads("gsr_project_backward_aux", out, layout)) return rc;
+    if (int rc = check_scene_args(scene, layout, n)) return rc;
+    // a frame of its own: the context's (the last rendered frame's) is left alone
+    Frame fr;
+    if (int rc = fill_frame(fr, cam, W, H, 1, 1, W, H, k)) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const gsr_record_grads ten{in->d_color, in->d_opacity, in->d_conic, in->d_center};
+    return project_backward_launch(c, scene, layout, n, fr, ten, *out, static_cast<hipStream_t>(stream), in->d_z);
+}
+
+extern "C" int gsr_render_backward_scene_aux(gsr_context* c, const void* scene, int layout, int64_t n,
+                                             const gsr_camera* cam, int W, int H, int nx, int ny, int ws, int hs,
+                                             float k, const gsr_aux_upstream* up, float* d_feat_grad,
+                                             float* d_scratch, const gsr_scene_grads* out, void* stream) {
+    if (!c) return set_err(GSR_E_ARG, "null context");
+    if (int rc = check_aux_upstream("gsr_render_backward_scene_aux", up, d_feat_grad)) return rc;
+    if (int rc = check_scene_grads("gsr_render_backward_scene_aux", out, layout)) return rc;
+    if (int rc = check_scene_args(scene, layout, n)) return rc;
+    {
+        Frame probe;   // the frame's argument errors, before the planes are zeroed
+        if (int rc = fill_frame(probe, cam, W, H, nx, ny, ws, hs, k)) return rc;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    float* planes = d_scratch;
+    if (!planes && n > 0) {
+        if (int rc = c->rec_grads.reserve(11 * per_gaussian(n))) return rc;   // eleven planes of n floats
+        planes = c->rec_grads;
+    }
+    if (n > 0) HIP_TRY(hipMemsetAsync(planes, 0, 11 * (size_t)n * sizeof(float), static_cast<hipStream_t>(stream)));
+    const gsr_record_grads_aux_out rg{planes, planes + 3 * n, planes + 4 * n, planes + 8 * n, planes + 10 * n,
+                                      d_feat_grad};
+    const int rc = aux_frame_locked(c, scene, layout, n, cam, W, H, nx, ny, ws, hs, k, stream,
+                                    [&] { return blend_backward_aux_locked(c, *up, rg); });
+    if (rc != GSR_OK && rc != GSR_E_OVERFLOW) return rc;
+    const gsr_record_grads in{planes, planes + 3 * n, planes + 4 * n, planes + 8 * n};
+    // (without a depth gradient the z plane stays zero: the ten-entry kernel)
+    const float* in_z = up->d_grad_depth ? planes + 10 * n : nullptr;
+    if (int r2 = project_backward_launch(c, scene, layout, n, c->fr, in, *out, c->stream, in_z)) return r2;
     return rc;
 }
 

@@ -379,6 +379,87 @@ int gsr_render_backward_scene(gsr_context* ctx, const void* d_scene, int layout,
                               float* d_record_scratch /* 10 planes of n floats, or NULL */,
                               const gsr_scene_grads* out, void* stream);
 
+/* The backward pass with gsr_render_aux's depth and feature planes: gsr_render_backward,
+ * gsr_project_backward and gsr_render_backward_scene with two more kinds of upstream
+ * gradient, so a loss may read every plane the renderer composites.
+ *
+ * gsr_render_backward_aux.  With g_D = d_grad_depth (the gradient of gsr_render_aux's d_depth,
+ * the UN-NORMALISED sum of -Z alpha T) and g_f = plane f of d_grad_feat (the gradient of
+ * d_feat_out plane f), W*H planes like the others, a NULL plane counting as zeros, the
+ * function differentiated is
+ *   L = sum over pixels of g_rgb . image + g_A alpha + g_D depth + sum_f g_f feat_f
+ * of the exact blend, with gsr_render_backward's take decisions (no gradient).  Let z_j = -Z_j
+ * be the float gsr_render_aux composites and phi_f,j = d_features[f * n + j].  With
+ *   u_j = g_rgb . colour_j + g_A + g_D z_j + sum_f g_f phi_f,j
+ * everything gsr_render_backward states holds as written: P_j, G, dL/dalpha_j = T_j u_j -
+ * (G - P_j) / (1 - alpha_j), the inactive clamp, d_color, d_opacity, d_conic, d_center.  Two
+ * more outputs, both linear:
+ *   d_z[i]            += sum over pixels of g_D alpha T     (dL/d(-Z_i))
+ *   d_feat[f * n + i] += sum over pixels of g_f alpha T     (dL/d phi_f,i)
+ * There is no normalised mode.  A loss on the expected depth D = depth / alpha with gradient g
+ * = dL/dD passes d_grad_depth = g / alpha and adds -g depth / alpha^2 to d_grad_alpha.
+ *
+ * Outputs are planar [c * n + i], ACCUMULATE, and are summed with float atomics: like
+ * gsr_render_backward's they are NOT reproducible bit for bit.  An output whose gradient is
+ * identically zero for want of an upstream is not touched (d_color without d_grad_image, d_z
+ * without d_grad_depth, d_feat without d_grad_feat), nor is a Gaussian no pixel composited.
+ * With d_grad_depth, d_grad_feat, d_z and d_feat all NULL and nfeat == 0 the call is
+ * gsr_render_backward: the same kernel at the same cost.
+ * Frame policy, incomplete frames and GSR_E_OVERFLOW are gsr_render_backward's.  Workspaces
+ * are gsr_render_aux's (-Z per Gaussian; the interleaved features above four), grown by
+ * high-water mark.  GSR_E_ARG, before any device work: up or out NULL; all four gradient
+ * inputs NULL; every output NULL; nfeat outside [0, GSR_AUX_MAX_FEATURES]; nfeat > 0 without
+ * d_features; d_grad_feat or out->d_feat with nfeat == 0; the frame arguments gsr_render
+ * refuses.
+ *
+ * gsr_project_backward_aux is gsr_project_backward with an eleventh upstream entry, d_z[i] =
+ * dL/d(-Z_i), Z = (V [p, 1])_z: it adds -V[2][j] d_z to the position gradient, and through the
+ * position to trbf_center and the motion arrays of a 4D block.  A Gaussian is skipped when all
+ * ELEVEN entries are +-0; every other rule, the reproducibility and the argument errors are
+ * gsr_project_backward's ("every input NULL" counts five).  With d_z NULL it is
+ * gsr_project_backward bit for bit.
+ *
+ * gsr_render_backward_scene_aux is the fused call over ELEVEN record planes (colour 3,
+ * opacity 1, conic 4, centre 2, z 1: the first ten where gsr_render_backward_scene has them),
+ * in d_record_scratch or a workspace of the context (11 n floats through this call only),
+ * zeroed on `stream` first.  Feature gradients have no scene array to go to: they are added to
+ * d_feat_grad (nfeat planes of n floats, ACCUMULATED, or NULL).  Errors as the two calls'. */
+typedef struct gsr_aux_upstream {      /* inputs */
+    const float* d_grad_image;  /* 3*W*H or NULL */
+    const float* d_grad_alpha;  /* W*H or NULL */
+    const float* d_grad_depth;  /* W*H or NULL */
+    const float* d_grad_feat;   /* nfeat*W*H planar or NULL */
+    const float* d_features;    /* nfeat arrays of n floats, as gsr_aux_targets; NULL iff nfeat == 0 */
+    int          nfeat;         /* 0..GSR_AUX_MAX_FEATURES */
+} gsr_aux_upstream;
+typedef struct gsr_record_grads_aux_out {  /* outputs, planar [c*n+i], ACCUMULATED, NULL = not computed */
+    float* d_color;    /* 3 planes */
+    float* d_opacity;  /* 1 */
+    float* d_conic;    /* 4 */
+    float* d_center;   /* 2 */
+    float* d_z;        /* n floats: dL/d(-Z) */
+    float* d_feat;     /* nfeat planes of n floats */
+} gsr_record_grads_aux_out;
+typedef struct gsr_record_grads_aux {      /* inputs of the projection; NULL = zeros */
+    const float* d_color;    /* 3 planes */
+    const float* d_opacity;  /* 1 */
+    const float* d_conic;    /* 4 */
+    const float* d_center;   /* 2 */
+    const float* d_z;        /* 1 */
+} gsr_record_grads_aux;
+int gsr_render_backward_aux(gsr_context* ctx, const void* d_scene, int layout, int64_t n, const gsr_camera* cam,
+                            int W, int H, int num_tile_x, int num_tile_y, int width_stride, int height_stride,
+                            float k, const gsr_aux_upstream* up, const gsr_record_grads_aux_out* out, void* stream);
+int gsr_project_backward_aux(gsr_context* ctx, const void* d_scene, int layout, int64_t n, const gsr_camera* cam,
+                             int W, int H, float k, const gsr_record_grads_aux* in, const gsr_scene_grads* out,
+                             void* stream);
+int gsr_render_backward_scene_aux(gsr_context* ctx, const void* d_scene, int layout, int64_t n,
+                                  const gsr_camera* cam, int W, int H, int num_tile_x, int num_tile_y,
+                                  int width_stride, int height_stride, float k, const gsr_aux_upstream* up,
+                                  float* d_feat_grad /* nfeat planes of n floats, ACCUMULATED, or NULL */,
+                                  float* d_record_scratch /* 11 planes of n floats, or NULL */,
+                                  const gsr_scene_grads* out, void* stream);
+
 /* Offline camera path (config 4 on one GPU; the reference has no batch entry
  * point — it renders one frame per preprocessCUDAGaussians call, render.cu:871):
  * frame i renders cams[i] (at times[i] for 4D scenes; times may be NULL) into
